@@ -14,6 +14,12 @@ configs[2]); super-k-mer buckets are routed to the partition's owner rank by gkc
 libgkc_hip.so, RCCL over xGMI), each rank counts the partitions it owns. The N=1 line also carries `config.share_of_8`: that same
 per-GPU share (1.25e8 reads, the partition count of the 8-GPU run, 4 pushes + exchanges through a one-rank RCCL communicator) timed
 on this GPU, i.e. the per-GPU cost of configs[2] before any byte moves over xGMI.
+
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` of the
+timed region). `--full` adds what takes runs or checks of its own: the verification of the results, the same K steps with the records left in HBM,
+the single-lane step, the roofline figures, the labelled blocks (k = 63, Bloom + MPHF, two passes, frequency order, skewed input, share of 8), the
+CPU baselines; the `--no-*` options trim that set. `--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy (float64): see
+dump_outputs().
 """
 import argparse
 import ctypes as C
@@ -136,7 +142,7 @@ def verify_block(c, expect, amin=1):
     return out
 
 
-REF_DIR = os.path.join(ROOT, "integration", "_build", "ref")      # unpatched reference tools built by integration/build_reference.sh (git-ignored, shipped by gpurun)
+REF_DIR = os.path.join(ROOT, "oracle", "_ref", "ref")      # unpatched reference tools built by oracle/build_ref.sh (git-ignored, they go with the checkout)
 
 
 def cpu_baseline_reference(c, k, n_reads=10_000_000):
@@ -349,6 +355,92 @@ def host_landed_leg(c, gkc, step, sync, distinct, n_steps=5, n_steps_amin2=5, ex
     return out
 
 
+DUMP_SEED = 20240607          # the partitions and records --dump-outputs samples
+DUMP_PARTS = 8
+DUMP_BYTES = 56 << 20         # the sampled records' share of the 64 MB the dump may take
+
+
+def dump_outputs(c, out_dir, parts, owned, from_sink):
+    """What the last timed step handed its caller, as float64 .npy files in out_dir (the same arguments give the same inputs, so two builds compare file by file):
+      stats.npy             [valid k-mers, distinct k-mers, solid records, super-k-mers] of the step
+      partition_sizes.npy   [parts]: Count records of every partition (0 for a partition another rank owns)
+      sample_index.npy      [n, 2]: (partition, record index) of each sampled record — DUMP_PARTS partitions drawn with DUMP_SEED, records drawn with
+                            (DUMP_SEED, partition) when a partition holds more than its share of DUMP_BYTES, kept in order
+      kmers.npy             [n, 2 | 4]: the sampled records' k-mer as 32-bit words, least significant first (exact in float64)
+      abundance.npy         [n]: their abundance
+    from_sink: the records are read where the host-landed step left them (the page-locked sink), else from the device."""
+    os.makedirs(out_dir, exist_ok=True)
+    st = c.stats()
+    words = 2 if c.rec_bytes == 16 else 4
+    sizes = np.zeros(parts, np.float64)
+    for p in owned:
+        sizes[p] = c.partition_info(0, p)[0]
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = sorted(int(p) for p in rng.choice(np.asarray(owned), size=min(DUMP_PARTS, len(owned)), replace=False))
+    per_part = DUMP_BYTES // ((words + 3) * 8) // max(1, len(pick))
+    idx, kmers, ab = [], [], []
+    for p in pick:
+        raw = c.wait_partition(0, p)[0] if from_sink else c.partition_records(0, p)
+        n = int(sizes[p])
+        if raw is None or n == 0:
+            continue
+        r = np.asarray(raw[: n * c.rec_bytes]).view(np.uint64).reshape(n, c.rec_bytes // 8)
+        rows = np.arange(n) if n <= per_part else np.sort(np.random.default_rng((DUMP_SEED, p)).choice(n, size=per_part, replace=False))
+        r = r[rows]
+        key = r[:, :words // 2]
+        w = np.empty((len(rows), words), np.float64)
+        for j in range(words // 2):
+            w[:, 2 * j] = key[:, j] & np.uint64(0xFFFFFFFF)
+            w[:, 2 * j + 1] = key[:, j] >> np.uint64(32)
+        idx.append(np.stack([np.full(len(rows), p, np.float64), rows.astype(np.float64)], axis=1)); kmers.append(w)
+        ab.append((r[:, words // 2] & np.uint64(0xFFFFFFFF)).astype(np.float64))
+    arrays = {"stats": np.array([st["kmers_nb_valid"], st["kmers_nb_distinct"], st["kmers_nb_solid"], st["nb_superkmers"]], np.float64),
+              "partition_sizes": sizes,
+              "sample_index": np.concatenate(idx) if idx else np.zeros((0, 2)),
+              "kmers": np.concatenate(kmers) if kmers else np.zeros((0, words)),
+              "abundance": np.concatenate(ab) if ab else np.zeros(0)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())), "sampled_partitions": pick}
+
+
+def workload_of(k, n_reads, m, parts, world):
+    if world > 1:
+        return ("BASELINE configs[2] at %d GPU(s): k=%d, %d synthetic 150 bp reads per GPU (%d in all), minimizer-partition exchange (gkc_exchange: RCCL send/recv over xGMI), "
+                "m=%d, %d partitions" % (world, k, n_reads, n_reads * world, m, parts))
+    return "k=%d, %d synthetic 150 bp reads per GPU, single-pass count (no Bloom), m=%d, %d partitions" % (k, n_reads, m, parts)
+
+
+def lean_line(args, c, chunks, rank, world, use_dist, red_dev, torch, dist, json_fd, value_mode, sink_why, dt, per, ktime, landed, dumped, names, workload):
+    """the line of a plain run (no --full): the headline of the K timed steps, nothing that takes a run or a check of its own"""
+    st = c.stats()
+    distinct, valid = st["kmers_nb_distinct"], st["kmers_nb_valid"]
+    if world > 1:
+        t = torch.tensor([distinct, valid], device=red_dev, dtype=torch.int64); dist.all_reduce(t); distinct, valid = int(t[0]), int(t[1])
+    if rank == 0:
+        out = {"metric": "distinct k-mers/s at k=%d" % args.k, "value": distinct / (dt / args.steps), "unit": "distinct k-mers/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64" if args.k <= 31 else "u128", "full": False,
+               "value_definition": ("SURVEY 8(d) wall: reads resident in HBM -> every distinct k-mer's Count record (abundance-min 1) in page-locked HOST memory; the timed K steps are "
+                                    "host-landed steps (PCIe-bound: see `landed`)" if value_mode == "host" else
+                                    "records left in HBM (no host sink: %s)" % (sink_why if sink_why else "GKC_BENCH_VALUE=device")),
+               "ms_per_step_median": float(np.median(per)),
+               "landed": landed,
+               "data": "synthetic (device generator, seeded; 150 bp reads, 30x, 1% substitutions)",
+               "config": {"workload": workload, "valid_kmers": valid, "distinct_kmers": distinct,
+                          "kernel_ms_per_step": {n_: round(ktime[n_][0] / args.steps, 3) for n_ in names}},
+               "note": "plain run: the results are not verified here; bench.py --full verifies them and adds the device-resident region, the roofline and the other blocks"}
+        if dumped is not None:
+            out["outputs"] = dumped
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    if value_mode == "host":
+        c.set_host_sink(None); c.set_sink_mode("packed")
+    for b_, o_, _, _ in chunks:
+        c.device_free(b_); c.device_free(o_)
+    if use_dist:
+        dist.barrier(); dist.destroy_process_group()
+
+
 def bind_to_gpu_numa_node(torch, local):
     """Several ranks on one host: this process (and with it the page-locked sink it allocates and the library's unpack threads, which follow the sink's node) goes to the
     NUMA node its GPU hangs on — 8 ranks left where the launcher put them tend to land on one socket and share ITS memory controllers for 8 x 100 GB per step.
@@ -390,6 +482,8 @@ def main():
     ap.add_argument("--no-two-pass", action="store_true", help="skip the two-pass block (Stage A of pass 1 overlapped with Stage B of pass 0)")
     ap.add_argument("--no-share-of-8", action="store_true", help="skip the N=1 block that times BASELINE configs[2]'s per-GPU share")
     ap.add_argument("--pushes", type=int, default=4, help="multi-GPU: pushes (and exchanges) per pass and rank")
+    ap.add_argument("--full", action="store_true", help="also run the checks, the device-resident region, the roofline and the labelled blocks (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64, < 64 MB in all)")
     args = ap.parse_args()
 
     # stdout carries exactly ONE JSON line: everything else that writes to fd 1 (RCCL prints its version banner there)
@@ -461,7 +555,7 @@ def main():
         # 64 MiB and 300 MiB (two chunks of the 256 MiB chunking) of a keyed pattern through the communicator's grouped ncclSend / ncclRecv path — the first thing
         # an 8-GPU run does with RCCL is a checked transfer, not the job. A mismatch or an RCCL error fails every rank loudly here.
         selftest = None
-        if os.environ.get("GKC_COMM_SELFTEST", "1" if world > 1 else "0") != "0":
+        if os.environ.get("GKC_COMM_SELFTEST", "1" if world > 1 and args.full else "0") != "0":
             selftest = {}
             for nb_ in (64 << 20, 300 << 20):
                 bad_, ms_ = runner.comm.selftest(nb_)
@@ -527,7 +621,7 @@ def main():
             sys.stderr.write("[bench rank %d] no host sink (%s): `value` is the HBM-resident figure\n" % (rank, sink_why))
     pcie_gbs = None; host_verification = None; landed = None
     if value_mode == "host":
-        pcie_gbs = pcie_probe(c, sink)
+        pcie_gbs = pcie_probe(c, sink) if args.full else None       # (a measurement of its own: --full)
         c.set_host_sink(sink)
         # Several ranks share ONE host: packed batches cost the link 0.4x but the host 104 B of DRAM traffic per record (6.3 B DMA-written, read again by the expansion
         # threads, 16 B of non-temporal stores) against 16 B raw — N ranks' expansion threads meet at the same memory controllers (tools/hostmem_probe/unpack_ranks_probe:
@@ -553,11 +647,21 @@ def main():
         landed = {"ms_per_step": dt_host / args.steps * 1e3, "ms_per_step_median": float(np.median(per_host)), "ms_steps": [round(x, 1) for x in per_host], "steps": args.steps,
                   "solid_records": st_h["kmers_nb_solid"], "bytes_landed": st_h["kmers_nb_solid"] * c.rec_bytes, "bytes_over_the_link": wire,
                   "packed_on_the_wire": st_h.get("sink_wire_bytes", 0) > 0, "pcie_d2h_GBps": pcie_gbs,
-                  "link_GBps_over_the_step": wire / (dt_host / args.steps) / 1e9, "frac_of_pcie": wire / (dt_host / args.steps) / 1e9 / pcie_gbs,
+                  "link_GBps_over_the_step": wire / (dt_host / args.steps) / 1e9, "frac_of_pcie": wire / (dt_host / args.steps) / 1e9 / pcie_gbs if pcie_gbs else None,
                   "sink_GB": sink.nbytes / 1e9, "sink_alloc_s": sink.alloc_s, "sink_overflow": "sink" in err_,
                   "sink_mode": sink_mode, "sink_mode_trial": sink_trial}
         if numa_note:
             landed["host_placement"] = numa_note
+    else:
+        dt, per_dev, ktime = timed_region(args.warmup, args.steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(c, args.dump_outputs, parts, list(runner.owned()) if runner is not None else list(range(parts)), value_mode == "host")
+    if not args.full:
+        return lean_line(args, c, chunks, rank, world, use_dist, red_dev, torch, dist, json_fd, value_mode, sink_why, dt_host if value_mode == "host" else dt,
+                         per_host if value_mode == "host" else per_dev, ktime_host if value_mode == "host" else ktime, landed, dumped, names,
+                         workload_of(k, n_reads, m, parts, world))
+    if value_mode == "host":
         # outside the clock: what landed is what the device holds (first / middle / last partition this rank owns)
         try:
             same = True
@@ -580,7 +684,6 @@ def main():
         dt, per_dev, ktime = timed_region(1, args.steps)             # the same K steps with the records left in HBM
         dt_value, ktime_value = dt_host, ktime_host
     else:
-        dt, per_dev, ktime = timed_region(args.warmup, args.steps)
         dt_value, ktime_value = dt, ktime
     st = c.stats()
     distinct = st["kmers_nb_distinct"]; valid = st["kmers_nb_valid"]
@@ -645,10 +748,7 @@ def main():
         keys_per_rank = valid / world
         key_bytes = 8 if k <= 31 else 16
         alg, dom, dom_ms, achieved, launches_per_step = kernel_roofline(ktime, args.steps, n_bases, st, k, keys_per_rank, distinct / world, dom_from=ktime_dev)
-        workload = ("k=%d, %d synthetic 150 bp reads per GPU, single-pass count (no Bloom), m=%d, %d partitions" % (k, n_reads, m, parts))
-        if world > 1:
-            workload = ("BASELINE configs[2] at %d GPU(s): k=%d, %d synthetic 150 bp reads per GPU (%d in all), minimizer-partition exchange (gkc_exchange: RCCL send/recv over xGMI), "
-                        "m=%d, %d partitions" % (world, k, n_reads, n_reads * world, m, parts))
+        workload = workload_of(k, n_reads, m, parts, world)
         traffic = None
         kname = {"scan_count": "k_scan_tile<false, 2, true, false>", "scan_emit": "k_emit_desc<2>", "expand_count": "k_expand_count<1, 2>",
                  "expand_scatter": "k_expand_scatter_pair", "bucket_sort": "k_wave_sort<1, true>", "compact": "k_gather_counts<1>", "dedupe_bin": "k_dedupe_bin<2>", "dedupe_sort": "k_dedupe_sort<2>"}
@@ -673,7 +773,7 @@ def main():
         out = {
             "metric": "distinct k-mers/s at k=%d" % k, "value": value, "unit": "distinct k-mers/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64" if k <= 31 else "u128",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64" if k <= 31 else "u128", "full": True,
             "value_definition": ("SURVEY 8(d) wall: reads resident in HBM -> every distinct k-mer's Count record (abundance-min 1) in page-locked HOST memory; the timed K steps are "
                                  "host-landed steps (PCIe-bound: see `landed`)" if value_mode == "host" else
                                  "records left in HBM (no host sink: %s)" % (sink_why if sink_why else "GKC_BENCH_VALUE=device")),
@@ -1039,11 +1139,13 @@ def main():
                 if ref_b is not None:
                     port_b["reference_attempt"] = ref_b
                 else:
-                    port_b["reference_attempt"] = "integration/_build/ref/dbgh5 absent (integration/build_reference.sh builds it from /root/reference)"
+                    port_b["reference_attempt"] = "oracle/_ref/ref/dbgh5 absent (oracle/build_ref.sh builds it from the reference sources)"
                 out["cpu_baseline"] = port_b
         elif world == 1:
             out["cpu_baseline"] = None
         out["all_blocks_verified"] = bool(all(all_verified))
+        if dumped is not None:
+            out["outputs"] = dumped
         os.write(json_fd, (json.dumps(out) + "\n").encode())
         if not all(all_verified):
             sys.stderr.write("bench.py: a timed block left results that are NOT the count of its input (see the `verified` fields)\n")

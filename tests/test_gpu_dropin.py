@@ -1,6 +1,6 @@
 """The drop-in end to end on the GPU box: the reference's OWN dbgh5 (main(), Configuration, Repartitor, processor chain, HDF5 storage), patched with
 integration/gatb-core.device.patch + integration/gatb_device/*.hpp and linked against libgkc_hip.so
-(integration/check_integration.sh --link -> integration/_build/dbgh5_device, a build-container artefact that travels with the repository snapshot), must write
+(integration/check_integration.sh --link -> oracle/_ref/dbgh5_device, a build-container artefact that travels with the repository snapshot), must write
 .h5 files whose datasets are exactly what the UNPATCHED reference wrote for the same input (tests/golden/reference_run/*.npz): every /dsk/solid/<p> in order,
 the histogram, the repartition table. Three ways through the binding:
   * bulk        the default chain: solidity window + histogram on the device, one block insert per partition (BagHDF5Patch::insert(const Item*, size_t));
@@ -9,7 +9,7 @@ the histogram, the repartition table. Three ways through the binding:
                 by default the text of a plain FASTA / FASTQ bank goes to the device as it is and is parsed there (gkc_push_fastx);
   * two ranks   two processes on the one GPU (the library's file-mailbox transport), reads shared out by index, super-k-mers exchanged, results gathered on
                 rank 0: ONE .h5 with every dataset of the single-process file (CountProcessorDump.hpp:85-95, GraphUnitigs.cpp:921-931).
-The files are read back with the reference's own gatb-h5dump (integration/_build/ref, built by integration/build_reference.sh). Where the artefacts are absent: FAILED on a GPU box (the build step that makes them did not run), skipped elsewhere."""
+The files are read back with the reference's own gatb-h5dump (oracle/_ref/ref, built by integration/build_reference.sh). Where the artefacts are absent: FAILED on a GPU box (the build step that makes them did not run), skipped elsewhere."""
 import os
 import subprocess
 import tempfile
@@ -22,8 +22,8 @@ from tests.test_reference_run import load
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "integration", "_build", "dbgh5_device")
-H5DUMP = os.path.join(ROOT, "integration", "_build", "ref", "gatb-h5dump")
+EXE = os.path.join(ROOT, "oracle", "_ref", "dbgh5_device")
+H5DUMP = os.path.join(ROOT, "oracle", "_ref", "ref", "gatb-h5dump")
 
 
 def _gpu_box():
@@ -163,7 +163,7 @@ def test_two_ranks_write_one_h5(tmp_path, tag, how):
                        "seq_size_max": str(max(len(x) for x in seqs))}, got
 
 
-DBGINFO = os.path.join(ROOT, "integration", "_build", "ref", "dbginfo")
+DBGINFO = os.path.join(ROOT, "oracle", "_ref", "ref", "dbginfo")
 
 
 def info_values(h5, keys):
@@ -364,7 +364,7 @@ def test_repartitor_sampling_runs_on_the_device(tmp_path, tag):
     assert np.array_equal(tables[0], tables[1])
 
 
-REF_DBGH5 = os.path.join(ROOT, "integration", "_build", "ref", "dbgh5")
+REF_DBGH5 = os.path.join(ROOT, "oracle", "_ref", "ref", "dbgh5")
 
 
 @needs_artefacts
@@ -405,8 +405,8 @@ def test_repartitor_stop_rules_against_the_unpatched_reference(tmp_path, freq):
         assert np.array_equal(dump_dataset(out["ref"][0], ds, "FILE"), dump_dataset(out["dev"][0], ds, "FILE"))
 
 
-UNITIGS = os.path.join(ROOT, "integration", "_build", "unitigs_check")            # GraphUnitigs linked WITH the patched units: counts on the device
-UNITIGS_REF = os.path.join(ROOT, "integration", "_build", "ref", "unitigs_check")  # GraphUnitigs of the unpatched library: the consumer of an .h5
+UNITIGS = os.path.join(ROOT, "oracle", "_ref", "unitigs_check")            # GraphUnitigs linked WITH the patched units: counts on the device
+UNITIGS_REF = os.path.join(ROOT, "oracle", "_ref", "ref", "unitigs_check")  # GraphUnitigs of the unpatched library: the consumer of an .h5
 
 
 def canonical_unitigs(fa):

@@ -12,6 +12,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("GATB_REFERENCE", "/root/reference/gatb-core")
 SCRIPT = os.path.join(ROOT, "integration", "check_integration.sh")
+WORK = os.environ.get("GKC_REFERENCE_WORK", os.path.join(os.environ.get("TMPDIR", "/tmp"), "gkc-reference-%d" % os.getuid()))      # the trees oracle/build_ref.sh
+SCRATCH = os.environ.get("GKC_INTEGRATION_SCRATCH", os.path.join(WORK, "integration"))                                                # (build()) leaves
+GATB_BUILD = os.environ.get("GATB_BUILD_DIR", os.path.join(WORK, "gatb_build"))
 
 needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "gatb")) or shutil.which("cmake") is None or shutil.which("g++") is None,
                                reason="reference sources / cmake / g++ not available here")
@@ -19,8 +22,7 @@ needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "gatb"
 
 @needs_ref
 def test_binding_compiles_against_the_reference_headers(tmp_path_factory):
-    scratch = os.environ.get("GKC_INTEGRATION_SCRATCH", "/tmp/gkc_integration")
-    out = subprocess.run(["bash", SCRIPT, scratch], capture_output=True, text=True, timeout=900)
+    out = subprocess.run(["bash", SCRIPT, SCRATCH], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
     assert "syntax ok" in out.stdout
 
@@ -42,11 +44,10 @@ def test_patch_file_is_what_the_generator_produces():
 
 
 @needs_ref
-@pytest.mark.skipif(not os.path.exists(os.environ.get("GATB_BUILD_DIR", "/tmp/gatb_build") + "/lib/Release/libgatbcore.a"),
+@pytest.mark.skipif(not os.path.exists(os.path.join(GATB_BUILD, "lib", "Release", "libgatbcore.a")),
                     reason="no built reference library (lib/Release/libgatbcore.a) to link against")
 def test_patched_dbgh5_links_against_libgkc():
-    scratch = os.environ.get("GKC_INTEGRATION_SCRATCH", "/tmp/gkc_integration")
-    out = subprocess.run(["bash", SCRIPT, scratch, "--link", os.environ.get("GATB_BUILD_DIR", "/tmp/gatb_build")], capture_output=True, text=True, timeout=1800)
+    out = subprocess.run(["bash", SCRIPT, SCRATCH, "--link", GATB_BUILD], capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
     assert "link ok" in out.stdout and "U gkc_wait_partition" in out.stdout and "U gkc_push_reads" in out.stdout
     assert "U gkc_bloom_insert_solid" in out.stdout and "U gkc_mphf_build_solid" in out.stdout and "U gkc_bloom_contains8" in out.stdout      # Bloom / MPHF / debloom hunks are in

@@ -79,12 +79,12 @@ def test_oracle_equals_reference_run(path):
 
 
 def test_fixtures_are_what_the_reference_built_from_this_repository_writes():
-    """tools/make_reference_run_vectors.py --check: the reference's own dbgh5 / gatb-h5dump (integration/_build/ref, built by integration/build_reference.sh from
+    """tools/make_reference_run_vectors.py --check: the reference's own dbgh5 / gatb-h5dump (oracle/_ref/ref, built by integration/build_reference.sh from
     /root/reference with the reference's cmake) run again on the generated inputs must write exactly the committed fixtures — the pin is reproducible from the
     repository (VERDICT r2 weak #1). Skipped where the reference tools are not built (the GPU box has them; /root/reference is not needed to RUN them)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "integration", "_build", "ref", "dbgh5")):
-        pytest.skip("integration/_build/ref absent (integration/build_reference.sh)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "ref", "dbgh5")):
+        pytest.skip("oracle/_ref/ref absent (integration/build_reference.sh)")
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "make_reference_run_vectors.py"), "--check"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "IDENTICAL" in r.stdout, (r.stdout + r.stderr)[-2000:]

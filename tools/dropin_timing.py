@@ -16,8 +16,8 @@ import numpy as np
 import __graft_entry__ as ge
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "integration", "_build", "ref")
-DEV = os.path.join(ROOT, "integration", "_build", "dbgh5_device")
+REF = os.path.join(ROOT, "oracle", "_ref", "ref")
+DEV = os.path.join(ROOT, "oracle", "_ref", "dbgh5_device")
 
 
 def info(h5):

@@ -1,4 +1,4 @@
-"""Golden vectors from the reference ITSELF: runs the reference's dbgh5 / gatb-h5dump binaries — integration/_build/ref/, built from /root/reference by
+"""Golden vectors from the reference ITSELF: runs the reference's dbgh5 / gatb-h5dump binaries — oracle/_ref/ref/, built from the reference sources by
 integration/build_reference.sh (the reference's own cmake; reproducible from this repository) — on small generated inputs and stores what they wrote as
 fixtures under tests/golden/reference_run/. The tests only read the committed fixtures.
 
@@ -20,7 +20,7 @@ sys.path.insert(0, ROOT)
 from tests.util import synth_reads  # noqa: E402
 
 _args = [a for a in sys.argv[1:] if not a.startswith("--")]
-_default_bin = os.path.join(ROOT, "integration", "_build", "ref")
+_default_bin = os.path.join(ROOT, "oracle", "_ref", "ref")
 BIN = _args[0] if _args else (_default_bin if os.path.exists(os.path.join(_default_bin, "dbgh5")) else "/tmp/gatb_build/bin/Release")
 COMMITTED = os.path.join(ROOT, "tests", "golden", "reference_run")
 CHECK = "--check" in sys.argv
@@ -97,7 +97,7 @@ def canonical_unitigs(fa):
 
 
 def run_unitigs(tag, reads, k):
-    """the reference's GraphUnitigs (integration/unitigs_check.cpp linked against the UNPATCHED library: integration/_build/ref/unitigs_check) on the .h5 the reference's
+    """the reference's GraphUnitigs (integration/unitigs_check.cpp linked against the UNPATCHED library: oracle/_ref/ref/unitigs_check) on the .h5 the reference's
     dbgh5 counted in the mode GraphUnitigs forces (-minimizer-type 1 -repartition-type 1, GraphUnitigs.cpp:861-870), and straight from the FASTA: the unitig set"""
     import json
     exe = os.path.join(BIN, "unitigs_check")

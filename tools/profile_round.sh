@@ -7,17 +7,17 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 # VRAM touched once (a fresh box pays ~26 ms per GB the first time a region is allocated: tools/alloc_probe)
 [ -x tools/alloc_probe/alloc_probe ] && tools/alloc_probe/alloc_probe malloc 16 16 > $OUT/${TAG}_vram_touch.txt 2>&1
 # 1. the driver's line
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_1gpu_1e8reads.json 2> $OUT/${TAG}_bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_1gpu_1e8reads.json 2> $OUT/${TAG}_bench.err
 # 2. kernel trace of the headline blocks (two lanes, host-landed region + device-resident region), k = 31
 LEAN="--no-k63 --no-two-pass --no-share-of-8 --no-cpu-baseline --no-bloom-mphf --no-freq-order --no-skewed"
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o r -- python bench.py --steps 5 --warmup 2 $LEAN > $OUT/${TAG}_kt_line.json 2> /dev/null
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt -o r -- python bench.py --full --steps 5 --warmup 2 $LEAN > $OUT/${TAG}_kt_line.json 2> /dev/null
 python tools/rocprof_summary.py $(find $OUT/${TAG}_kt -name "*.db" | head -1) > $OUT/${TAG}_kernel_stats_1e8reads.txt
 # 3. k = 63, two lanes (tools/prof_step.py: 3 steps, the first one cold)
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_kt63 -o r -- python tools/prof_step.py 100000000 8192 63 > $OUT/${TAG}_k63_steps.txt 2> /dev/null
 python tools/rocprof_summary.py $(find $OUT/${TAG}_kt63 -name "*.db" | head -1) > $OUT/${TAG}_kernel_stats_k63_1e8reads.txt
 # 4. PMC: separate passes, one Stage-B lane, records left in HBM; the command runs 2 steps (1 untimed + 1 timed)
 for C in FETCH_SIZE WRITE_SIZE; do
-  GKC_STAGEB_LANES=1 GKC_BENCH_VALUE=device rocprofv3 --pmc $C --kernel-trace -d $OUT/${TAG}_pmc_$C -o r -- python bench.py --steps 1 --warmup 0 $LEAN --no-host-landed > $OUT/${TAG}_pmc_${C}_line.json 2> /dev/null
+  GKC_STAGEB_LANES=1 GKC_BENCH_VALUE=device rocprofv3 --pmc $C --kernel-trace -d $OUT/${TAG}_pmc_$C -o r -- python bench.py --full --steps 1 --warmup 0 $LEAN --no-host-landed > $OUT/${TAG}_pmc_${C}_line.json 2> /dev/null
 done
 WL=$(python -c "import json;print(json.load(open('$OUT/${TAG}_pmc_FETCH_SIZE_line.json'))['config']['workload'])")
 python tools/pmc_traffic.py $(find $OUT/${TAG}_pmc_FETCH_SIZE -name "*.db" | head -1) $(find $OUT/${TAG}_pmc_WRITE_SIZE -name "*.db" | head -1) "$WL" $OUT/${TAG}_pmc_traffic.json 2 > /dev/null

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 LEAN="--no-k63 --no-two-pass --no-share-of-8 --no-cpu-baseline --no-bloom-mphf --no-freq-order --no-skewed"
 # ---- 1
 for R in 1000000 5000000; do
-  GKC_BENCH_BACKEND=gloo timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 8 --steps 3 --warmup 1 --reads $R \
+  GKC_BENCH_BACKEND=gloo timeout 1200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 8 --steps 3 --warmup 1 --reads $R \
       > $OUT/r06_bench_8ranks_dryrun_${R}.json 2> $OUT/r06_bench_8ranks_dryrun_${R}.err
   tail -c 300 $OUT/r06_bench_8ranks_dryrun_${R}.json; echo; grep -E "communicator|sink" $OUT/r06_bench_8ranks_dryrun_${R}.err | head -5
 done
@@ -26,7 +26,7 @@ for MODE in 0 1; do
 done
 # ---- 3
 for DIV in 4 8 16 32; do
-  GKC_SINK_FIRST_DIV=$DIV python bench.py --steps 8 --warmup 2 $LEAN > $OUT/r06_leadin_div$DIV.json 2> /dev/null
+  GKC_SINK_FIRST_DIV=$DIV python bench.py --full --steps 8 --warmup 2 $LEAN > $OUT/r06_leadin_div$DIV.json 2> /dev/null
   python - <<PY
 import json
 d = json.load(open("$OUT/r06_leadin_div$DIV.json"))

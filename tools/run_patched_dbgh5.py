@@ -1,5 +1,5 @@
 """(run on the GPU box, then `--compare` here)  The reference's OWN dbgh5, patched with integration/SortingCountAlgorithm.device.patch and linked against libgkc_hip.so
-(integration/check_integration.sh --link -> integration/_build/dbgh5_device, a build-container artefact that travels with gpurun), run on the
+(integration/check_integration.sh --link -> oracle/_ref/dbgh5_device, a build-container artefact that travels with oracle/_ref/), run on the
 GPU box on the inputs of the reference-run fixtures: the .h5 it writes must hold exactly the datasets the unpatched reference wrote
 (tests/golden/reference_run/*.npz). This is the drop-in claim end to end: reference main(), reference Configuration / Repartitor / processors /
 HDF5 storage, counting on the MI355X through PartitionsByDeviceCommand. Optional evidence (the artefact only exists where the reference was
@@ -16,7 +16,7 @@ sys.path.insert(0, ROOT)
 from tests.h5mini import H5Mini                       # noqa: E402
 from tests.test_reference_run import load             # noqa: E402
 
-EXE = os.path.join(ROOT, "integration", "_build", "dbgh5_device")
+EXE = os.path.join(ROOT, "oracle", "_ref", "dbgh5_device")
 CASES = [("k21_freq_4parts", ["-minimizer-type", "1", "-repartition-type", "1"], "1"),
          ("k21_lexi_grouped_parts", ["-repartition-type", "1"], "1"),
          ("k21_default_parts", [], "1"),
@@ -55,7 +55,7 @@ def compare(outdir, bin_dir):
 
 def main():
     if not os.path.exists(EXE):
-        print("no integration/_build/dbgh5_device (run integration/check_integration.sh --link in the build container)"); return 2
+        print("no oracle/_ref/dbgh5_device (run integration/check_integration.sh --link in the build container)"); return 2
     outdir = sys.argv[1] if len(sys.argv) > 1 else tempfile.mkdtemp()
     if len(sys.argv) > 2 and sys.argv[2] == "--compare":
         return compare(outdir, sys.argv[3] if len(sys.argv) > 3 else "/tmp/gatb_build/bin/Release")

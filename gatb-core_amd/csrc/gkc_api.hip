@@ -98,7 +98,6 @@ void gkc_ctx_child_add(gkc_ctx* c) { std::lock_guard<std::mutex> lk(c->mu); c->c
 int gkc_alloc_histo(gkc_ctx* c)
 {
     const size_t bytes = (size_t)std::max<uint32_t>(c->nb_passes, 1) * ((size_t)c->histo_max + 1) * 8;
-    c->d_histo.release();
     GKC_TRY(c->ensure(c->d_histo, bytes));
     GKC_HIP(c, hipMemset(c->d_histo.p, 0, bytes));
     return GKC_OK;
@@ -200,16 +199,13 @@ static void ctx_destroy_now(gkc_ctx* c)
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     if (c->fetch_stream) { (void)hipStreamSynchronize(c->fetch_stream); (void)hipStreamDestroy(c->fetch_stream); }
     for (hipEvent_t e : c->landed_events) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; i++) { c->h2d_bases[i].release(); c->h2d_offs[i].release(); if (c->h2d_copied[i]) (void)hipEventDestroy(c->h2d_copied[i]); if (c->h2d_scanned[i]) (void)hipEventDestroy(c->h2d_scanned[i]); }
+    for (int i = 0; i < 2; i++) { if (c->h2d_copied[i]) (void)hipEventDestroy(c->h2d_copied[i]); if (c->h2d_scanned[i]) (void)hipEventDestroy(c->h2d_scanned[i]); }
     clear_segments(c);
     std::vector<uint32_t> passes; for (auto& kv : c->pass_outputs) passes.push_back(kv.first);
     for (uint32_t p : passes) free_pass_outputs(c, p);
-    c->d_mkey_lut.release(); c->d_key2val.release(); c->d_repart.release(); c->d_repart_coarse.release(); c->d_histo.release();
-    c->d_scan_counters.release(); c->d_rsbits.release(); c->d_scan_matrix.release(); c->d_desc.release(); c->d_desc_tile.release();
-    c->pool.destroy();
     (void)hipStreamDestroy(c->stream);
     for (hipStream_t st : c->lane_streams) if (st) (void)hipStreamDestroy(st);
-    delete c;
+    delete c;                                  // the context's DevBuf members return their blocks, then its pool frees everything (member order: gkc_common.hpp)
 }
 
 const char* gkc_last_error(const gkc_ctx* c) { return c ? c->err.msg.c_str() : g_create_error.c_str(); }
@@ -392,7 +388,6 @@ int gkc_push_reads_device(gkc_ctx* c, const char* d_bases, const uint64_t* d_off
         r0 = r1; base0 = base1;
     }
     (void)hipStreamSynchronize(c->stream);
-    d_off.release();
     return rc;
 }
 
@@ -463,12 +458,11 @@ static int upload_reads(gkc_ctx* c, const char* bases, const uint64_t* offsets, 
     if (!offsets || offsets[0] != 0) GKC_FAIL(c, GKC_ERR_ARG, "offsets[0] must be 0");
     *n_bases = offsets[n_reads];
     GKC_TRY(c->ensure(db, (size_t)*n_bases + 64));
-    int rc = c->ensure(dof, (size_t)(n_reads + 1) * 8);
-    if (rc != GKC_OK) { db.release(); return rc; }
+    GKC_TRY(c->ensure(dof, (size_t)(n_reads + 1) * 8));
     hipError_t e = hipSuccess;
     if (*n_bases) e = hipMemcpyAsync(db.p, bases, (size_t)*n_bases, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dof.p, offsets, (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream);
-    if (e != hipSuccess) { db.release(); dof.release(); GKC_FAIL(c, GKC_ERR_HIP, "H2D copy failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "H2D copy failed: %s", hipGetErrorString(e));
     return GKC_OK;
 }
 
@@ -481,7 +475,6 @@ int gkc_sample_minimizers(gkc_ctx* c, const char* bases, const uint64_t* offsets
     GKC_TRY(upload_reads(c, bases, offsets, n_reads, db, dof, &nb));
     int rc = gkc_scan_sample(c, (const char*)db.p, (const uint64_t*)dof.p, n_reads, nb, superkmers_per_minim, kmers_per_minim);
     (void)hipStreamSynchronize(c->stream);
-    db.release(); dof.release();
     return rc;
 }
 
@@ -504,7 +497,6 @@ int gkc_count_mmers(gkc_ctx* c, uint32_t m, const char* bases, const uint64_t* o
     GKC_TRY(upload_reads(c, bases, offsets, n_reads, db, dof, &nb));
     int rc = gkc_scan_count_mmers(c, m, (const char*)db.p, (const uint64_t*)dof.p, n_reads, counts);
     (void)hipStreamSynchronize(c->stream);
-    db.release(); dof.release();
     return rc;
 }
 
@@ -842,7 +834,6 @@ int gkc_kmer_checksum_device(gkc_ctx* c, const char* d_bases, const uint64_t* d_
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h, d.p, 16, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    d.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "checksum kernel failed: %s", hipGetErrorString(e));
     if (checksum) *checksum = h[0];  if (n_valid) *n_valid = h[1];
     return GKC_OK;

@@ -379,12 +379,12 @@ int gkc_bloom_create(gkc_ctx* c, int kind, uint64_t tai_bits, uint32_t nb_hash, 
     const size_t bytes = (size_t)((b->nchar + 3) / 4 * 4 + 8);
     int rc = c->ensure(b->bits, bytes);
     if (rc != GKC_OK) { delete b; return rc; }
-    if (hipMemsetAsync(b->bits.p, 0, bytes, c->stream) != hipSuccess) { b->bits.release(); delete b; GKC_FAIL(c, GKC_ERR_HIP, "memset failed"); }
+    if (hipMemsetAsync(b->bits.p, 0, bytes, c->stream) != hipSuccess) { delete b; GKC_FAIL(c, GKC_ERR_HIP, "memset failed"); }
     gkc_ctx_child_add(c);
     *out = b;
     return GKC_OK;
 }
-void gkc_bloom_destroy(gkc_bloom* b) { if (b) { gkc_ctx* c = b->ctx; b->bits.release(); delete b; gkc_ctx_child_release(c); } }
+void gkc_bloom_destroy(gkc_bloom* b) { if (b) { gkc_ctx* c = b->ctx; delete b; gkc_ctx_child_release(c); } }
 int gkc_bloom_allreduce_or(gkc_bloom* b, gkc_comm* m)
 {
     if (!b || !m) return GKC_ERR_ARG;
@@ -430,7 +430,6 @@ static int bloom_insert_arrays(gkc_bloom* b, const BSeg* segs, uint32_t n_segs, 
     const uint32_t n_wgs = (uint32_t)std::min<uint64_t>(BR_WGS, (total + BR_THREADS - 1) / BR_THREADS);
     const uint64_t chunk = (total + n_wgs - 1) / n_wgs;
     DevBuf d_wg, d_tot, d_off, d_items;
-    struct Guard { DevBuf *a, *b2, *c2, *d; ~Guard() { a->release(); b2->release(); c2->release(); d->release(); } } guard{&d_wg, &d_tot, &d_off, &d_items};
     GKC_TRY(c->ensure(d_wg, (size_t)n_wgs * n_regions * 4)); GKC_TRY(c->ensure(d_tot, (size_t)n_regions * 4)); GKC_TRY(c->ensure(d_off, ((size_t)n_regions + 1) * 4));
     GKC_TRY(c->ensure(d_items, b->kind == 0 ? (size_t)n_virtual * 4 : (size_t)total * sizeof(BloomItem)));
     static bool attr_set = false;
@@ -486,7 +485,6 @@ int gkc_bloom_insert(gkc_bloom* b, const void* keys, uint64_t n, uint32_t stride
     hipError_t e = hipMemcpyAsync(d.p, keys, (size_t)n * stride, hipMemcpyHostToDevice, c->stream);
     int rc = (e == hipSuccess) ? gkc_bloom_insert_device(b, d.p, n, stride) : GKC_ERR_HIP;
     (void)hipStreamSynchronize(c->stream);
-    d.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "H2D copy failed: %s", hipGetErrorString(e));
     return rc;
 }
@@ -524,7 +522,6 @@ static int bloom_contains8_regions(gkc_bloom* b, const BSeg* segs, uint32_t n_se
     const uint32_t n_wgs = (uint32_t)std::min<uint64_t>(BR_WGS, (total + BR_THREADS - 1) / BR_THREADS);
     const uint64_t chunk = (total + n_wgs - 1) / n_wgs;
     DevBuf d_wg, d_tot, d_off, d_items, d_sides;
-    struct Guard { DevBuf *a, *b2, *c2, *d, *e; ~Guard() { a->release(); b2->release(); c2->release(); d->release(); e->release(); } } guard{&d_wg, &d_tot, &d_off, &d_items, &d_sides};
     GKC_TRY(c->ensure(d_wg, (size_t)n_wgs * n_regions * 4)); GKC_TRY(c->ensure(d_tot, (size_t)n_regions * 4)); GKC_TRY(c->ensure(d_off, ((size_t)n_regions + 1) * 4));
     GKC_TRY(c->ensure(d_items, (size_t)total * 2 * sizeof(BloomQ))); GKC_TRY(c->ensure(d_sides, (size_t)total * 2));
     static bool attr_set = false;
@@ -556,8 +553,7 @@ static int bloom_query(gkc_bloom* b, const void* keys, uint64_t n, uint32_t stri
     if (c8 && b->kind != 2) GKC_FAIL(c, GKC_ERR_ARG, "contains8 is implemented by the neighbor kind only (Bloom.hpp:245-250 throws ExceptionNotImplemented)");
     if (!n) return GKC_OK;
     DevBuf d, o; GKC_TRY(c->ensure(d, (size_t)n * stride));
-    int rc = c->ensure(o, (size_t)n);
-    if (rc != GKC_OK) { d.release(); return rc; }
+    GKC_TRY(c->ensure(o, (size_t)n));
     hipError_t e = hipMemcpyAsync(d.p, keys, (size_t)n * stride, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         ScopedTimer tm(c, c8 ? "bloom_contains8" : "bloom_contains");
@@ -571,7 +567,6 @@ static int bloom_query(gkc_bloom* b, const void* keys, uint64_t n, uint32_t stri
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, o.p, (size_t)n, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    d.release(); o.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "bloom query failed: %s", hipGetErrorString(e));
     return GKC_OK;
 }
@@ -598,8 +593,7 @@ int gkc_bloom_query_solid(gkc_bloom* b, gkc_ctx* c, int neighbors8, uint8_t* d_o
     if (!total) return GKC_OK;
     DevBuf tmp, acc;
     if (!d_out) { GKC_TRY(c->ensure(tmp, (size_t)total)); d_out = (uint8_t*)tmp.p; }
-    int rc = c->ensure(acc, 8);
-    if (rc != GKC_OK) { tmp.release(); return rc; }
+    GKC_TRY(c->ensure(acc, 8));
     hipError_t e = hipMemsetAsync(acc.p, 0, 8, c->stream);
     {   ScopedTimer tm(c, neighbors8 ? "bloom_contains8" : "bloom_contains");
         uint64_t done = 0;
@@ -634,7 +628,6 @@ int gkc_bloom_query_solid(gkc_bloom* b, gkc_ctx* c, int neighbors8, uint8_t* d_o
     if (e == hipSuccess) { hipLaunchKernelGGL(k_sum_bits8, dim3(1024), dim3(256), 0, c->stream, (const uint8_t*)d_out, total, (unsigned long long*)acc.p); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipMemcpyAsync(&h, acc.p, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    tmp.release(); acc.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "bloom query failed: %s", hipGetErrorString(e));
     if (n_positive) *n_positive = h;
     return GKC_OK;

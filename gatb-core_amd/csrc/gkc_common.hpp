@@ -87,6 +87,9 @@ struct GkcTun {
     }
 };
 inline GkcTun& gkc_tun() { static GkcTun t = [] { GkcTun x; x.read(); return x; }(); return t; }
+// Who reads what, and when: gkc_count_pass copies the snapshot ONCE at entry and hands that copy to its plan, its batches and their sink calls — a refresh by
+// gkc_begin_pass of the next pass (gkc_finish_pass_async) cannot change a value between two reads of one batch. Still read in place: DevPool's own switches
+// (vmm*, pool_debug, pool_trace), Stage A, and the Bloom / MPHF / communicator entry points, each of which refreshes on entry and runs on the caller's thread.
 inline void gkc_tun_refresh() { static std::mutex mu; std::lock_guard<std::mutex> lk(mu); GkcTun x; x.read(); gkc_tun() = x; }
 
 // Stage B runs batches on two host threads, each with its own stream: the thread-local override routes every launch / copy / timer of
@@ -229,11 +232,22 @@ struct DevPool {
     }
     bool is_mapped(void* p) { std::lock_guard<std::recursive_mutex> lk(mu); return vmm.count(p) != 0; }
     void trim() { std::lock_guard<std::recursive_mutex> lk(mu); for (auto& kv : cache) raw_free(kv.second); cache.clear(); cached_bytes = 0; }
+    // everything goes, blocks still handed out included (a context's result blocks and arenas are plain pointers): no DevBuf of this pool may be alive and non-empty
+    // after this — its destructor would free the block a second time — which is why the pool of a context is the first member to be built and the last to go
     void destroy() { std::lock_guard<std::recursive_mutex> lk(mu); trim(); for (auto& kv : live) raw_free(kv.first); live.clear(); }
+    ~DevPool() { destroy(); }
 };
 
+// Owns its block: handed back to the pool (or hipFree) when the DevBuf goes out of scope. Move-only; release() (idempotent) hands the block back before that.
+// A DevBuf must be empty or gone before its pool is: the context declares its pool ahead of its DevBuf members, and the objects built on a context (gkc_bloom,
+// gkc_mphf, gkc_comm) are deleted before they let go of it (gkc_ctx_child_release).
 struct DevBuf {
     void* p = nullptr; size_t bytes = 0; DevPool* pool = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), pool(o.pool) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; pool = o.pool; o.p = nullptr; o.bytes = 0; } return *this; }
+    ~DevBuf() { release(); }
     void release() { if (p) { if (pool) pool->free(p); else (void)hipFree(p); p = nullptr; bytes = 0; } }
 };
 
@@ -262,6 +276,7 @@ struct gkc_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     gkc_error err{0, ""};
+    DevPool pool;                          // ahead of every DevBuf member: members go in reverse order, so the buffers return their blocks before the pool frees them
     // model
     bool configured = false;
     uint32_t k = 0, m = 0, nb_partitions = 0, nb_passes = 1;
@@ -318,7 +333,6 @@ struct gkc_ctx {
     std::mutex mu;                         // shared bookkeeping (timing, stats, outputs, error text) when Stage B runs two lanes
     hipStream_t lane_streams[3] = {nullptr, nullptr, nullptr};   // extra Stage-B lanes (created on first use)
     std::vector<uint8_t> pass_released;       // gkc_release_pass was called for the pass: whole-context consumers of the results refuse to run
-    uint64_t slots_hint = 0;                  // key slots the big working buffers of a Stage-B batch are sized for (the pass's batch budget)
     double d_hint = 0;                        // solid records per key of the last Stage-B pass (0 = none yet): sizes the next pass's batches
     std::map<std::string, Timing> timing;
     // scratch reused across calls
@@ -334,7 +348,7 @@ struct gkc_ctx {
         std::lock_guard<std::mutex> lk(err_mu); err.code = code; err.msg = buf;
     }
     std::mutex err_mu;
-    DevPool pool;
+    // (re)allocates b when it is empty or too small. The CONTENTS of b are undefined afterwards, whether the block is new, reused from the pool or the one b held.
     int ensure(DevBuf& b, size_t bytes) {
         if (b.bytes >= bytes && b.p && (pool.vmm_ok || !pool.is_mapped(b.p))) return GKC_OK;      // (a mapped range kept from before the communicator: replaced by a hipMalloc block)
         b.release();
@@ -377,15 +391,15 @@ int gkc_scan_count_mmers(gkc_ctx* c, uint32_t m, const char* d_bases, const uint
 int gkc_export_superkmers(gkc_ctx* c, uint32_t part, uint8_t* out, uint64_t cap, uint64_t* nb, uint64_t* nsk, uint64_t* nk);
 
 int gkc_require_resident(gkc_ctx* c, const char* who);
-// packed result batches (gkc_sink.hip)
-bool  gkc_sink_packed(gkc_ctx* c);
-bool  gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records);   // several ranks on one host: landed, unexpanded records beyond 1.5 batches -> this batch travels raw
+// packed result batches (gkc_sink.hip). tun: the tunables the call works with — a Stage-B lane hands in its pass's snapshot, everyone else gkc_tun()
+bool  gkc_sink_packed(gkc_ctx* c, const GkcTun& tun);
+bool  gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records, const GkcTun& tun);   // several ranks on one host: landed, unexpanded records beyond 1.5 batches -> this batch travels raw
 int   gkc_sink_prepare(gkc_ctx* c);
 void  gkc_sink_reset(gkc_ctx* c);
 void  gkc_sink_drain(gkc_ctx* c);
 void  gkc_sink_shutdown(gkc_ctx* c);
 void  gkc_sink_wait_batch(gkc_ctx* c, const void* batch);
-void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot, const std::vector<uint64_t>& solid_prefix, uint8_t* h_dest);
+void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot, const std::vector<uint64_t>& solid_prefix, uint8_t* h_dest, const GkcTun& tun);
 const char* gkc_sink_last_refusal();                          // why this thread's last gkc_sink_send_packed returned nullptr
 struct gkc_comm;                              // gkc_dist.hip
 int gkc_comm_world(gkc_comm* m);

@@ -26,6 +26,7 @@
 //   taken from one queue by two host threads, each on its own stream (gkc_count_pass).
 #include "gkc_common.hpp"
 #include "gkc_device.hpp"
+#include "gkc_pass_plan.hpp"
 #include <algorithm>
 #include <mutex>
 #include <thread>
@@ -2141,12 +2142,11 @@ __global__ __launch_bounds__(DDCap<RW>::WAVES * 64) void k_dedupe_sort(uint64_t*
 
 // ------------------------------------------------------------------------------------------------ host orchestration
 constexpr uint32_t PART_ALIGN = 256;            // a partition's slot range starts on a multiple of this many slots
-// weight bits of a batch whose partitions all have at least min_bits sub-bucket bits (see the note at the top of the file). GKC_WEIGHT_BITS (tests, experiments)
+static_assert(GKC_OK == 0, "PassPlan keeps the first error of a pass as a plain int, 0 = none");
+// weight bits of a batch whose partitions all have at least min_bits sub-bucket bits (see the note at the top of the file). env = GKC_WEIGHT_BITS (tests, experiments)
 // asks for a number; it is honoured as far as the keys stay valid.
-static int weight_bits_env() { return gkc_tun().weight_bits; }
-template <int KW> static uint32_t weight_bits_of(uint32_t k, uint32_t min_bits)
+template <int KW> static uint32_t weight_bits_of(uint32_t k, uint32_t min_bits, int env)
 {
-    const int env = weight_bits_env();
     const int stored = 64 * KW, drop_ok = (int)std::min<uint32_t>(min_bits, (uint32_t)WEIGHT_DROP_MAX);
     const int valid = std::min<int>(WEIGHT_BITS_MAX, stored + drop_ok - 2 * (int)k);               // >= WEIGHT_BITS_MIN for every k the key width is used for
     int wb = valid;
@@ -2156,24 +2156,38 @@ template <int KW> static uint32_t weight_bits_of(uint32_t k, uint32_t min_bits)
 }
 constexpr int DEEP_FIXED = 4;                   // split levels launched unconditionally (a level with an empty queue returns at once); more only if the last one left work
 constexpr int DEEP_COUNTERS = 8;                // per-level counter triples (next level's queue length, sort list length, item ticket), used cyclically
-struct BatchBufs {
-    DevBuf pd, keysA, keysB, cnt, cnt8, b_start, b_n, b_cons, l_big, l_wg, l_split, misc, nd, ns, off_d, off_s, chunk, q[2], sitems, giant, glist, rbase, rroot, rcnt, dd_arena, dd_base, dd_bins, dd_lg, dd_off, dd_ptr, dd_end, pidx, ptot, order, vpd, vstart, vtail, vdone;
-    void release() { DevBuf* all[] = { &pd, &keysA, &keysB, &cnt, &cnt8, &b_start, &b_n, &b_cons, &l_big, &l_wg, &l_split, &misc, &nd, &ns, &off_d, &off_s, &chunk, &q[0], &q[1], &sitems, &giant, &glist, &rbase, &rroot, &rcnt, &dd_arena, &dd_base, &dd_bins, &dd_lg, &dd_off, &dd_ptr, &dd_end, &pidx, &ptot, &order, &vpd, &vstart, &vtail, &vdone };
-                     for (DevBuf* d : all) d->release(); }
+// tier capacities of a key width
+template <int KW> struct TierCaps {
+    static constexpr uint32_t CAP1 = WaveCapT1<KW>::CAP, CAP2 = WaveCapHuge<KW>::CAP;
+    static constexpr int K1 = WaveCapHuge<KW>::KPL / 2;
+    static constexpr uint32_t C1 = 4 * 64 * K1;                             // workgroup tier: 4 waves x 64 x K1 keys (4096 / 2048)
 };
 
-template <int KW, int RW>
-static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segment>& segments, const std::vector<uint32_t>& batch_parts, const std::vector<uint64_t>& part_keys,
-                       const SegTable& segs, std::vector<void*>& outputs)
-{   // (pass, segments: what this Stage B was started for — Stage A may have moved the context on to the next pass meanwhile: gkc_finish_pass_async)
-    typedef typename KeyT<KW>::type key_t;
-    const uint32_t nb = (uint32_t)batch_parts.size();
-    const uint32_t k = c->k;
-    // --- host-built tables (sizes are known exactly from Stage A)
-    std::vector<PartDesc> pd(nb);
-    std::vector<uint64_t> pidx(nb + 1);
+// Everything about a batch that the host decides before the first launch (sizes are known exactly from Stage A). Host data only.
+struct BatchLayout {
+    uint32_t nb = 0, k = 0;                       // partitions of the batch
+    bool dedupe = false, sliced = false;
+    std::vector<PartDesc> pd;                     // [nb]
+    std::vector<uint64_t> pidx;                   // [nb + 1] first sub-bucket of every partition
     uint64_t n_slots = 0, n_sub = 0;
-    const int dedupe_env = gkc_tun().dedupe;       // 0: never, 1: always, default: until a batch shows it does not pay
+    uint32_t min_bits1 = 64, max_bits_b = 0;      // fewest / most sub-bucket bits of a partition of the batch
+    std::vector<PartDesc> vpd; uint64_t slice_words = 0;      // sliced batch: the expansion's work list, 2^s entries per partition, each a share of its records
+    uint32_t nv = 0;                              // entries the expansion kernels walk (nb, or vpd.size())
+    uint32_t wb = 0, drop = 0, wcap = 0;          // weight bits; top bits of a key that fall off the stored word; copies one merged record may stand for
+    bool tag = false;                             // the f64-tagged sorting network orders the batch's keys
+    uint32_t cap3 = 0; uint64_t list_cap = 0;
+    std::vector<uint32_t> order;                  // [nv] entries, largest first (LPT)
+};
+
+// dedupe_allowed: GKC_DEDUPE and the context's own verdict (gkc_ctx::dedupe_off) leave the record deduplication on. Returns GKC_OK, or an error code with its text in err.
+template <int KW, int RW>
+static int batch_layout(const uint32_t k, const std::vector<uint32_t>& batch_parts, const std::vector<uint64_t>& part_keys, const bool dedupe_allowed, const GkcTun& tun, BatchLayout& L, std::string& err)
+{
+    const uint32_t nb = (uint32_t)batch_parts.size();
+    L.nb = nb; L.k = k;
+    L.pd.resize(nb); L.pidx.resize(nb + 1);
+    std::vector<PartDesc>& pd = L.pd;
+    uint64_t n_slots = 0, n_sub = 0;
     // Sliced batch (see SliceTables): a partition beyond GKC_SLICE_MIN k-mers (default 8e6: twice and more what the batches and the drop-in's Configuration aim
     // at, and where the bins of the record deduplication are full) is expanded by up to 16 workgroups, so that an entry is 2e6 .. 4e6 k-mers like a planned
     // partition; GKC_SLICES=0 switches it off (tests lower the threshold). The record deduplication (one workgroup per partition, bins for <= 8e5 records: on such
@@ -2181,24 +2195,24 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
     // Measured, 1e8 reads, k = 31, two lanes (profiles/r04_sliced_partitions.txt): 256 partitions 600 -> 375 ms per step (expand_count 109 -> 19 ms, expand_scatter
     // 238 -> 90 ms single lane; what is left of the gap to the 4096-partition step, 203 ms, is the split levels: every 2^13-th of such a partition is 5700 keys,
     // beyond the sort tiers), 64 partitions 387 ms, 1024 partitions 346 -> 323 ms.
-    const uint64_t slice_min = gkc_tun().slice_min;
+    const uint64_t slice_min = tun.slice_min;
     const uint64_t slice_keys = std::max<uint64_t>(1, slice_min / 4);
-    const bool slices_on = gkc_tun().slices;
     bool sliced = false; uint64_t heavy_keys = 0, batch_keys = 0;
-    if (slices_on) for (uint32_t i = 0; i < nb; i++) { const uint64_t np = part_keys[batch_parts[i]]; batch_keys += np; if (np > slice_min) { sliced = true; heavy_keys += np; } }
+    if (tun.slices) for (uint32_t i = 0; i < nb; i++) { const uint64_t np = part_keys[batch_parts[i]]; batch_keys += np; if (np > slice_min) { sliced = true; heavy_keys += np; } }
     // (one heavy partition among a thousand planned ones — a repeat family under one minimizer — does not cost the batch its deduplication: its single dedupe workgroup
     // hides behind the others; the step is skipped where most of the batch's k-mers sit in such partitions)
-    const bool dedupe = ((KW == 1 && RW == 2) || (KW == 2 && RW == 4 && k >= 32)) && dedupe_env != 0 && (dedupe_env == 1 || !c->dedupe_off) && nb > 0 && !(sliced && 2 * heavy_keys > batch_keys);
+    const bool dedupe = ((KW == 1 && RW == 2) || (KW == 2 && RW == 4 && k >= 32)) && dedupe_allowed && nb > 0 && !(sliced && 2 * heavy_keys > batch_keys);
+    L.dedupe = dedupe; L.sliced = sliced;
     // mean keys of a level-1 bucket, counted in k-mers BEFORE identical records are merged: with the merge on (8-byte keys: ~1.8x fewer keys on 30x reads) twice as
     // many — 12 sub-bucket bits instead of 13 for the partitions of the 1e8-read bench: first sort tier 46.8 -> 38.3 ms, the larger tiers +8, scatter -4: 220 -> 214 ms
     // (possible since the tagged sort carries 61 key bits: profiles/r04_weight_bits_experiment.txt)
     const uint32_t target = (KW == 1) ? (dedupe ? 2 * SUB_TARGET : SUB_TARGET) : SUB_TARGET / 2;
-    const uint32_t max_bits1 = gkc_tun().max_sub_bits >= 0 ? (uint32_t)gkc_tun().max_sub_bits : (uint32_t)MAX_SUB_BITS;
-    const uint32_t wb_goal = weight_bits_of<KW>(k, max_bits1);
+    const uint32_t max_bits1 = tun.max_sub_bits >= 0 ? (uint32_t)tun.max_sub_bits : (uint32_t)MAX_SUB_BITS;
+    const uint32_t wb_goal = weight_bits_of<KW>(k, max_bits1, tun.weight_bits);
     const int stored_or_mantissa = KTagBits<KW>::value;      // (16-byte keys: 125, which covers the 128 - 2k - wb >= -2 the dropped top bits need)
     const uint32_t need_goal = (uint32_t)std::min<int>((int)max_bits1, std::max<int>(0, 2 * (int)k + (int)wb_goal - stored_or_mantissa));
     const uint32_t need_min = (uint32_t)std::min<int>((int)max_bits1, std::max<int>(0, 2 * (int)k + WEIGHT_BITS_MIN - stored_or_mantissa));
-    bool goal_ok = weight_bits_env() != 0;              // (weight bits asked for: the sub-bucket bits they need, whatever the sizes)
+    bool goal_ok = tun.weight_bits != 0;                // (weight bits asked for: the sub-bucket bits they need, whatever the sizes)
     {   uint64_t tot = 0; for (uint32_t i = 0; i < nb; i++) tot += part_keys[batch_parts[i]];
         const uint64_t mean = nb ? tot / nb : 0;
         uint32_t bm = 0; while (bm < max_bits1 && (mean >> bm) > target) bm++;
@@ -2206,7 +2220,7 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
     }
     for (uint32_t i = 0; i < nb; i++) {
         const uint64_t np = part_keys[batch_parts[i]];
-        if (np >= (1ULL << 32)) GKC_FAIL(c, GKC_ERR_ARG, "partition %u holds %llu k-mers (>= 2^32): use more partitions", batch_parts[i], (unsigned long long)np);
+        if (np >= (1ULL << 32)) { err = "partition " + std::to_string(batch_parts[i]) + " holds " + std::to_string(np) + " k-mers (>= 2^32): use more partitions"; return GKC_ERR_ARG; }
         uint32_t bits = 0;
         while (bits < max_bits1 && bits < 2 * k && (np >> bits) > target) bits++;
         // 8-byte keys: a small partition still gets enough sub-buckets for what is left of a key below the sub-bucket index (k-mer + weight bits) to fit the 61 bits the
@@ -2214,88 +2228,138 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
         // weight bits the batch could have at best (wb_goal) if its MEAN partition is within one bit of what they need, else with the smallest weights. At k = 31
         // that is 4 / 3 bits (rounds 2-3, 52-bit tag: 13 / 12 bits whatever the partition's size — the 8-GPU share on one GPU, 32768 partitions of 4.5e5 k-mers,
         // 325 -> 278 ms when the tag was widened). (16-byte keys at k = 63: one sub-bucket bit at least, so that the third weight bit can push the key's top bit out.)
-        if (gkc_tun().max_sub_bits < 0) bits = std::min<uint32_t>(std::max(bits, goal_ok ? need_goal : need_min), 2 * k);
+        if (tun.max_sub_bits < 0) bits = std::min<uint32_t>(std::max(bits, goal_ok ? need_goal : need_min), 2 * k);
         pd[i].part = batch_parts[i]; pd[i].sub_bits = bits; pd[i].shift = 2 * k - bits; pd[i].pad = 0; pd[i].aux = 0;
         pd[i].key_base = n_slots; pd[i].sub_base = n_sub;
-        pidx[i] = n_sub;
+        L.pidx[i] = n_sub;
         n_slots += (np + (3ull << bits) + PART_ALIGN - 1) / PART_ALIGN * PART_ALIGN;       // sub-buckets start on multiples of 4 slots (pair scatter)
         n_sub += (1ull << bits);
     }
-    pidx[nb] = n_sub;
-    if (n_sub >= (1ULL << 31)) GKC_FAIL(c, GKC_ERR_ARG, "too many sub-buckets in one batch");
-    uint32_t min_bits1 = 64, max_bits_b = 0; for (uint32_t i = 0; i < nb; i++) { min_bits1 = std::min(min_bits1, pd[i].sub_bits); max_bits_b = std::max(max_bits_b, pd[i].sub_bits); }
+    L.pidx[nb] = n_sub;
+    if (n_sub >= (1ULL << 31)) { err = "too many sub-buckets in one batch"; return GKC_ERR_ARG; }
+    L.n_slots = n_slots; L.n_sub = n_sub;
+    for (uint32_t i = 0; i < nb; i++) { L.min_bits1 = std::min(L.min_bits1, pd[i].sub_bits); L.max_bits_b = std::max(L.max_bits_b, pd[i].sub_bits); }
     // the expansion's work list: one entry per partition, or (sliced batch) 2^s entries per partition, each a share of its records
-    std::vector<PartDesc> vpd; std::vector<uint32_t> v_parent; uint64_t slice_words = 0;
+    std::vector<uint32_t> v_parent;
     if (sliced) for (uint32_t i = 0; i < nb; i++) {
         const uint64_t np = part_keys[batch_parts[i]];
         uint32_t sb = 0; while (sb < 4 && np > slice_min && (np >> sb) > slice_keys) sb++;
         for (uint32_t w = 0; w < (1u << sb); w++) {
-            PartDesc e = pd[i]; e.pad = (sb << 16) | w; e.aux = slice_words; slice_words += 1ull << e.sub_bits;
-            vpd.push_back(e); v_parent.push_back(i);
+            PartDesc e = pd[i]; e.pad = (sb << 16) | w; e.aux = L.slice_words; L.slice_words += 1ull << e.sub_bits;
+            L.vpd.push_back(e); v_parent.push_back(i);
         }
     }
-    const uint32_t nv = sliced ? (uint32_t)vpd.size() : nb;
-    const uint32_t wb = weight_bits_of<KW>(k, nb ? min_bits1 : 0u);
-    const uint32_t drop = 2 * k + wb > 64u * KW ? 2 * k + wb - 64u * KW : 0u;      // top bits of a key that fall off the stored word (<= WEIGHT_DROP_MAX <= min_bits1)
-    const uint32_t wcap = drop >= 2 ? (1u << wb) - 1u : (1u << wb);                // copies one merged record may stand for (see the note at the top of the file)
-    constexpr uint32_t CAP1 = WaveCapT1<KW>::CAP, CAP2 = WaveCapHuge<KW>::CAP;
-    constexpr int K1 = WaveCapHuge<KW>::KPL / 2;
-    constexpr uint32_t C1 = 4 * 64 * K1;                                    // workgroup tier: 4 waves x 64 x K1 keys (4096 / 2048)
+    const uint32_t nv = L.nv = sliced ? (uint32_t)L.vpd.size() : nb;
+    L.wb = weight_bits_of<KW>(k, nb ? L.min_bits1 : 0u, tun.weight_bits);
+    L.drop = 2 * k + L.wb > 64u * KW ? 2 * k + L.wb - 64u * KW : 0u;        // top bits of a key that fall off the stored word (<= WEIGHT_DROP_MAX <= min_bits1)
+    L.wcap = L.drop >= 2 ? (1u << L.wb) - 1u : (1u << L.wb);                // copies one merged record may stand for (see the note at the top of the file)
+    // every bucket's keys share their top min_bits1 bits: when the rest fits a double's 52-bit mantissa the in-lane exchanges run as v_min/max_f64
+    // (16-byte keys, round 4: the same tag on the key's top word — v_min/max_f64 there, selects on the low word: KTag<2>)
+    L.tag = 2 * k + L.wb <= (uint32_t)KTagBits<KW>::value + L.min_bits1 && !tun.no_f64;
+    constexpr uint32_t CAP1 = TierCaps<KW>::CAP1, CAP2 = TierCaps<KW>::CAP2, C1 = TierCaps<KW>::C1;
     // measured (ms per 1.2e10 keys, workgroup tier + split levels + their sorts): up to 4096 keys in the workgroup tier: 40, up to 8192: 44, none: 47
-    const uint32_t wg_max = gkc_tun().wg_max ? std::min<uint32_t>(gkc_tun().wg_max, C1) : C1;
-    const uint32_t cap3 = std::max(wg_max, CAP2);                           // sub-buckets beyond are split again
-    const uint64_t list_cap = n_slots / CAP1 + nb + 1;                      // sub-buckets beyond the first tier / pieces beyond it at any split level
-    BatchBufs B;
-#define CB_TRY(expr) do { int rc__ = (expr); if (rc__ != GKC_OK) { B.release(); return rc__; } } while (0)
-#define CB_HIP(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { B.release(); c->set_error(GKC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__); return GKC_ERR_HIP; } } while (0)
-    CB_TRY(c->ensure(B.pd, nb * sizeof(PartDesc)));
-    // the big working buffers are sized for the pass's batch budget, not for this batch: every batch then asks the allocator for exactly
-    // the same blocks (a batch one partition larger or smaller would otherwise land in the next size class now and then)
-    const uint64_t alloc_slots = std::max<uint64_t>(std::max<uint64_t>(n_slots, c->slots_hint), 4);
-    CB_TRY(c->ensure(B.keysA, (size_t)alloc_slots * sizeof(key_t))); CB_TRY(c->ensure(B.keysB, (size_t)alloc_slots * sizeof(key_t)));
-    CB_TRY(c->ensure(B.cnt, (size_t)alloc_slots * 4)); CB_TRY(c->ensure(B.cnt8, (size_t)alloc_slots));
-    CB_TRY(c->ensure(B.b_start, (size_t)n_sub * 8)); CB_TRY(c->ensure(B.b_n, (size_t)n_sub * 4)); CB_TRY(c->ensure(B.b_cons, (size_t)n_sub));
-    CB_TRY(c->ensure(B.l_big, (size_t)list_cap * 4)); CB_TRY(c->ensure(B.l_wg, (size_t)list_cap * 4)); CB_TRY(c->ensure(B.l_split, (size_t)list_cap * 4));
-    CB_TRY(c->ensure(B.q[0], (size_t)list_cap * sizeof(DeepItem))); CB_TRY(c->ensure(B.q[1], (size_t)list_cap * sizeof(DeepItem)));
-    CB_TRY(c->ensure(B.misc, 64 * 4));
-    CB_TRY(c->ensure(B.nd, (size_t)std::max<uint64_t>(n_sub, 1) * 4));
-    const bool all_solid = c->amin <= 1 && c->amax == 0x7fffffff;
-    if (!all_solid) CB_TRY(c->ensure(B.ns, (size_t)std::max<uint64_t>(n_sub, 1) * 4));
-    CB_TRY(c->ensure(B.off_d, (size_t)(n_sub + 1) * 8)); CB_TRY(c->ensure(B.off_s, (size_t)(n_sub + 1) * 8));
-    CB_TRY(c->ensure(B.pidx, (size_t)(nb + 1) * 8)); CB_TRY(c->ensure(B.ptot, (size_t)(nb + 1) * 16));
+    const uint32_t wg_max = tun.wg_max ? std::min<uint32_t>(tun.wg_max, C1) : C1;
+    L.cap3 = std::max(wg_max, CAP2);                                        // sub-buckets beyond are split again
+    L.list_cap = n_slots / CAP1 + nb + 1;                                   // sub-buckets beyond the first tier / pieces beyond it at any split level
     // the expansion kernels run one workgroup per partition: workgroup i takes the i-th LARGEST partition, so that the launch does not end on one long
     // workgroup (partition sizes spread 2-3x around their mean). Only the assignment changes: the layout of the batch stays in partition order.
-    std::vector<uint32_t> order(nv);
-    for (uint32_t i = 0; i < nv; i++) order[i] = i;
-    const bool lpt = gkc_tun().batch_lpt;
-    auto keys_of_entry = [&](uint32_t v) -> uint64_t { return sliced ? part_keys[batch_parts[v_parent[v]]] >> (vpd[v].pad >> 16) : part_keys[batch_parts[v]]; };
-    if (lpt) std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return keys_of_entry(a) > keys_of_entry(b); });
-    CB_TRY(c->ensure(B.order, (size_t)nv * 4));
-    CB_HIP(hipMemcpyAsync(B.order.p, order.data(), (size_t)nv * 4, hipMemcpyHostToDevice, cur_stream(c)));
-    CB_HIP(hipMemcpyAsync(B.pd.p, pd.data(), nb * sizeof(PartDesc), hipMemcpyHostToDevice, cur_stream(c)));
-    SliceTables ST{ nullptr, nullptr, nullptr };
-    if (sliced) {
-        CB_TRY(c->ensure(B.vpd, (size_t)nv * sizeof(PartDesc))); CB_TRY(c->ensure(B.vstart, (size_t)slice_words * 4)); CB_TRY(c->ensure(B.vtail, (size_t)slice_words * 4)); CB_TRY(c->ensure(B.vdone, (size_t)nv * 4));
-        CB_HIP(hipMemcpyAsync(B.vpd.p, vpd.data(), (size_t)nv * sizeof(PartDesc), hipMemcpyHostToDevice, cur_stream(c)));
-        CB_HIP(hipMemsetAsync(B.vdone.p, 0, (size_t)nv * 4, cur_stream(c)));
-        ST.start = (uint32_t*)B.vstart.p; ST.tail = (uint32_t*)B.vtail.p; ST.done = (uint32_t*)B.vdone.p;
-    }
-    const PartDesc* const d_entries = sliced ? (const PartDesc*)B.vpd.p : (const PartDesc*)B.pd.p;          // what the expansion kernels walk
-    CB_HIP(hipMemcpyAsync(B.pidx.p, pidx.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
-    CB_HIP(hipMemsetAsync(B.misc.p, 0, 64 * 4, cur_stream(c)));
-    CB_HIP(hipMemsetAsync(B.nd.p, 0, (size_t)std::max<uint64_t>(n_sub, 1) * 4, cur_stream(c)));
-    if (!all_solid) CB_HIP(hipMemsetAsync(B.ns.p, 0, (size_t)std::max<uint64_t>(n_sub, 1) * 4, cur_stream(c)));
-    uint32_t* const misc = (uint32_t*)B.misc.p;          // [0] big [1] wg [2] split list lengths [3] giants [4] root chunks [5] ticket, [8 ..) counter triples of the split levels (cyclic)
-    TierLists T{};
-    T.big_list = (uint32_t*)B.l_big.p; T.big_count = misc + 0; T.wg_list = (uint32_t*)B.l_wg.p; T.wg_count = misc + 1;
-    T.split_list = (uint32_t*)B.l_split.p; T.split_count = misc + 2; T.cap1 = CAP1; T.cap2 = CAP2; T.cap3 = cap3;
-    CB_TRY(c->ensure(B.glist, GIANT_MAX * 4));
-    T.giant_list = (uint32_t*)B.glist.p; T.giant_count = misc + 3;
+    L.order.resize(nv);
+    for (uint32_t i = 0; i < nv; i++) L.order[i] = i;
+    auto keys_of_entry = [&](uint32_t v) -> uint64_t { return sliced ? part_keys[batch_parts[v_parent[v]]] >> (L.vpd[v].pad >> 16) : part_keys[batch_parts[v]]; };
+    if (tun.batch_lpt) std::stable_sort(L.order.begin(), L.order.end(), [&](uint32_t a, uint32_t b) { return keys_of_entry(a) > keys_of_entry(b); });
+    return GKC_OK;
+}
 
-    // Identical super-k-mer records of a partition are merged first (8-byte keys; see k_dedupe_*): the expansion then reads the batch's own deduplicated copy
-    SegTable segs_b = segs;
+struct BatchBufs {
+    DevBuf pd, keysA, keysB, cnt, cnt8, b_start, b_n, b_cons, l_big, l_wg, l_split, misc, nd, ns, off_d, off_s, chunk, q[2], sitems, giant, glist, rbase, rroot, rcnt, dd_arena, dd_base, dd_bins, dd_lg, dd_off, dd_ptr, dd_end, pidx, ptot, order, vpd, vstart, vtail, vdone;
+};
+
+// One batch on its way through Stage B: the layout, the device buffers (back to the pool when the run goes out of scope, on every path) and what one step hands to
+// the next. The steps are called once each, in the order they are declared, by count_batch.
+template <int KW, int RW>
+struct BatchRun {
+    typedef typename KeyT<KW>::type key_t;
+    static constexpr uint32_t CAP1 = TierCaps<KW>::CAP1, CAP2 = TierCaps<KW>::CAP2, C1 = TierCaps<KW>::C1;
+    static constexpr int K1 = TierCaps<KW>::K1;
+    static constexpr int OW = (KW == 1) ? 2 : 4;                              // words of a Count record
+    static constexpr bool FT = true;
+    gkc_ctx* const c; const uint32_t pass; const GkcTun& tun; const BatchLayout& L;
+    const std::vector<uint32_t>& batch_parts; const std::vector<uint64_t>& part_keys;
+    const uint32_t nb, k; const uint64_t n_slots, n_sub;
+    const bool all_solid;
+    const uint32_t deep_bits;                                                // tests: few bits per level force many levels
+    const uint64_t sort_cap;                                                 // an item of n keys lists <= 2 n / (cap1 / 2) + 1 runs and pieces
+    const unsigned deep_grid;
     std::vector<uint64_t> dd_base_h, dd_off_h; const void* dd_arena_h = nullptr;      // sources of asynchronous copies: alive until the batch is through
-    if (dedupe) {
+    std::vector<uint64_t> ptot;                                              // [nb + 1] (distinct, solid) prefixes of the partitions
+    uint32_t h_misc[64];
+    BatchBufs B;                                                             // (declared behind the host tables above: the buffers go first, and their return to the pool waits for the lane's stream)
+    uint32_t* misc = nullptr;            // [0] big [1] wg [2] split list lengths [3] giants [4] root chunks [5] ticket, [8 ..) counter triples of the split levels (cyclic)
+    TierLists T{}; SortOut O{}; SliceTables ST{ nullptr, nullptr, nullptr };
+    SegTable segs_b;                                                         // what the expansion reads: the pass's segments, or the batch's own deduplicated copy
+    const PartDesc* d_entries = nullptr;                                     // what the expansion kernels walk
+    key_t *keysA = nullptr, *keysB = nullptr; const uint64_t* bs = nullptr; const uint32_t* bn = nullptr; const uint8_t* bc = nullptr;
+    int level = DEEP_FIXED;                                                  // split levels launched so far
+    uint64_t total_solid = 0; void* out = nullptr;                           // the batch's Count records
+    const uint8_t* h_base = nullptr; hipEvent_t landed = nullptr; const void* sink_batch = nullptr;      // ... and where they went in the host sink
+
+    BatchRun(gkc_ctx* c_, uint32_t pass_, const GkcTun& tun_, const BatchLayout& L_, const std::vector<uint32_t>& batch_parts_, const std::vector<uint64_t>& part_keys_, const SegTable& segs)
+        : c(c_), pass(pass_), tun(tun_), L(L_), batch_parts(batch_parts_), part_keys(part_keys_), nb(L_.nb), k(L_.k), n_slots(L_.n_slots), n_sub(L_.n_sub),
+          all_solid(c_->amin <= 1 && c_->amax == 0x7fffffff), deep_bits(tun_.deep_bits),
+          sort_cap(L_.n_slots / (CAP1 / 4) + L_.list_cap + 64 + (uint64_t)GIANT_MAX * MAX_SUB),
+          deep_grid((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(L_.list_cap, 256 * 8))), ptot((size_t)(L_.nb + 1) * 2), segs_b(segs) {}
+
+    uint32_t* counters_of(int lv) const { return misc + 8 + 4 * (lv % DEEP_COUNTERS); }     // [0] items for the next level [1] pieces to sort [2] ticket
+
+    // --- working buffers, host-built tables to the device, counters cleared
+    int upload(const uint64_t slots_hint)
+    {
+        GKC_TRY(c->ensure(B.pd, nb * sizeof(PartDesc)));
+        // the big working buffers are sized for the pass's batch budget, not for this batch: every batch then asks the allocator for exactly
+        // the same blocks (a batch one partition larger or smaller would otherwise land in the next size class now and then)
+        const uint64_t alloc_slots = std::max<uint64_t>(std::max<uint64_t>(n_slots, slots_hint), 4);
+        const uint64_t list_cap = L.list_cap; const uint32_t nv = L.nv;
+        GKC_TRY(c->ensure(B.keysA, (size_t)alloc_slots * sizeof(key_t))); GKC_TRY(c->ensure(B.keysB, (size_t)alloc_slots * sizeof(key_t)));
+        GKC_TRY(c->ensure(B.cnt, (size_t)alloc_slots * 4)); GKC_TRY(c->ensure(B.cnt8, (size_t)alloc_slots));
+        GKC_TRY(c->ensure(B.b_start, (size_t)n_sub * 8)); GKC_TRY(c->ensure(B.b_n, (size_t)n_sub * 4)); GKC_TRY(c->ensure(B.b_cons, (size_t)n_sub));
+        GKC_TRY(c->ensure(B.l_big, (size_t)list_cap * 4)); GKC_TRY(c->ensure(B.l_wg, (size_t)list_cap * 4)); GKC_TRY(c->ensure(B.l_split, (size_t)list_cap * 4));
+        GKC_TRY(c->ensure(B.q[0], (size_t)list_cap * sizeof(DeepItem))); GKC_TRY(c->ensure(B.q[1], (size_t)list_cap * sizeof(DeepItem)));
+        GKC_TRY(c->ensure(B.misc, 64 * 4));
+        GKC_TRY(c->ensure(B.nd, (size_t)std::max<uint64_t>(n_sub, 1) * 4));
+        if (!all_solid) GKC_TRY(c->ensure(B.ns, (size_t)std::max<uint64_t>(n_sub, 1) * 4));
+        GKC_TRY(c->ensure(B.off_d, (size_t)(n_sub + 1) * 8)); GKC_TRY(c->ensure(B.off_s, (size_t)(n_sub + 1) * 8));
+        GKC_TRY(c->ensure(B.pidx, (size_t)(nb + 1) * 8)); GKC_TRY(c->ensure(B.ptot, (size_t)(nb + 1) * 16));
+        GKC_TRY(c->ensure(B.order, (size_t)nv * 4));
+        GKC_HIP(c, hipMemcpyAsync(B.order.p, L.order.data(), (size_t)nv * 4, hipMemcpyHostToDevice, cur_stream(c)));
+        GKC_HIP(c, hipMemcpyAsync(B.pd.p, L.pd.data(), nb * sizeof(PartDesc), hipMemcpyHostToDevice, cur_stream(c)));
+        if (L.sliced) {
+            GKC_TRY(c->ensure(B.vpd, (size_t)nv * sizeof(PartDesc))); GKC_TRY(c->ensure(B.vstart, (size_t)L.slice_words * 4)); GKC_TRY(c->ensure(B.vtail, (size_t)L.slice_words * 4)); GKC_TRY(c->ensure(B.vdone, (size_t)nv * 4));
+            GKC_HIP(c, hipMemcpyAsync(B.vpd.p, L.vpd.data(), (size_t)nv * sizeof(PartDesc), hipMemcpyHostToDevice, cur_stream(c)));
+            GKC_HIP(c, hipMemsetAsync(B.vdone.p, 0, (size_t)nv * 4, cur_stream(c)));
+            ST.start = (uint32_t*)B.vstart.p; ST.tail = (uint32_t*)B.vtail.p; ST.done = (uint32_t*)B.vdone.p;
+        }
+        d_entries = L.sliced ? (const PartDesc*)B.vpd.p : (const PartDesc*)B.pd.p;
+        GKC_HIP(c, hipMemcpyAsync(B.pidx.p, L.pidx.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
+        GKC_HIP(c, hipMemsetAsync(B.misc.p, 0, 64 * 4, cur_stream(c)));
+        GKC_HIP(c, hipMemsetAsync(B.nd.p, 0, (size_t)std::max<uint64_t>(n_sub, 1) * 4, cur_stream(c)));
+        if (!all_solid) GKC_HIP(c, hipMemsetAsync(B.ns.p, 0, (size_t)std::max<uint64_t>(n_sub, 1) * 4, cur_stream(c)));
+        misc = (uint32_t*)B.misc.p;
+        T.big_list = (uint32_t*)B.l_big.p; T.big_count = misc + 0; T.wg_list = (uint32_t*)B.l_wg.p; T.wg_count = misc + 1;
+        T.split_list = (uint32_t*)B.l_split.p; T.split_count = misc + 2; T.cap1 = CAP1; T.cap2 = CAP2; T.cap3 = L.cap3;
+        GKC_TRY(c->ensure(B.glist, GIANT_MAX * 4));
+        T.giant_list = (uint32_t*)B.glist.p; T.giant_count = misc + 3;
+        O.cnt8 = (uint8_t*)B.cnt8.p; O.cnt32 = (uint32_t*)B.cnt.p; O.histo = c->histo_of(pass); O.histo_max = c->histo_max;
+        O.nd = (uint32_t*)B.nd.p; O.ns = all_solid ? (uint32_t*)B.nd.p : (uint32_t*)B.ns.p; O.amin = c->amin; O.amax = c->amax; O.all_solid = all_solid ? 1u : 0u;
+        O.wb = L.wb;
+        keysA = (key_t*)B.keysA.p; keysB = (key_t*)B.keysB.p;
+        bs = (const uint64_t*)B.b_start.p; bn = (const uint32_t*)B.b_n.p; bc = (const uint8_t*)B.b_cons.p;
+        return GKC_OK;
+    }
+
+    // --- identical super-k-mer records of a partition are merged first (8-byte keys; see k_dedupe_*): the expansion then reads the batch's own deduplicated copy
+    int dedupe(const std::vector<Segment>& segments, const SegTable& segs)
+    {
+        if (!L.dedupe) return GKC_OK;
         unsigned long long* const dd_totals = reinterpret_cast<unsigned long long*>(misc + 40);     // k-mers into / out of the deduplication of this batch
         const uint32_t Pn = segs.P, p_first = batch_parts.front(), p_last = batch_parts.back();
         std::vector<uint64_t>& base = dd_base_h; std::vector<uint64_t>& off = dd_off_h; base.assign(nb + 1, 0); off.assign((size_t)Pn + 1, 0);
@@ -2310,39 +2374,44 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
         }
         const uint64_t total_recs = base[nb];
         bool fits = total_recs > 0; for (uint32_t i = 0; i < nb; i++) fits = fits && (base[i + 1] - base[i]) < (1ULL << 31);
-        if (fits) {
-            CB_TRY(c->ensure(B.dd_arena, (size_t)total_recs * RW * 8)); CB_TRY(c->ensure(B.dd_base, (size_t)(nb + 1) * 8)); CB_TRY(c->ensure(B.dd_bins, (size_t)nb * (DD_BINS_MAX + 1) * 4));
-            CB_TRY(c->ensure(B.dd_lg, (size_t)nb * 4)); CB_TRY(c->ensure(B.dd_off, ((size_t)Pn + 1) * 8)); CB_TRY(c->ensure(B.dd_ptr, 8));
-            const void*& arena_p = dd_arena_h; arena_p = B.dd_arena.p;
-            CB_HIP(hipMemcpyAsync(B.dd_base.p, base.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
-            CB_HIP(hipMemcpyAsync(B.dd_off.p, off.data(), ((size_t)Pn + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
-            CB_HIP(hipMemcpyAsync(B.dd_ptr.p, &arena_p, 8, hipMemcpyHostToDevice, cur_stream(c)));
-            DedupeTables DT{ (uint32_t*)B.dd_bins.p, (uint32_t*)B.dd_lg.p };
-            {   ScopedTimer tm(c, "dedupe_bin");
-                hipLaunchKernelGGL((k_dedupe_bin<RW>), dim3(std::min(nb, 512u)), dim3(DD_THREADS), 0, cur_stream(c), (const PartDesc*)B.pd.p, segs, k, (const uint64_t*)B.dd_base.p,
-                                   (uint64_t*)B.dd_arena.p, DT, nb, misc + 5);
-            }
-            CB_TRY(c->ensure(B.dd_end, (size_t)Pn * 8));
-            ScopedTimer tm(c, "dedupe_sort");
-            hipLaunchKernelGGL((k_dedupe_sort<RW>), dim3(std::min(nb, 512u)), dim3(DDCap<RW>::WAVES * 64), 0, cur_stream(c), (uint64_t*)B.dd_arena.p, (const uint64_t*)B.dd_base.p, DT, (const PartDesc*)B.pd.p,
-                               (uint64_t*)B.dd_end.p, nb, misc + 44, dd_totals, wcap);
-            CB_HIP(hipGetLastError());
-            segs_b.rec = (const uint8_t* const*)B.dd_ptr.p; segs_b.rec_off = (const uint64_t*)B.dd_off.p; segs_b.n_seg = 1; segs_b.rec_end = (const uint64_t*)B.dd_end.p;
+        if (!fits) return GKC_OK;
+        GKC_TRY(c->ensure(B.dd_arena, (size_t)total_recs * RW * 8)); GKC_TRY(c->ensure(B.dd_base, (size_t)(nb + 1) * 8)); GKC_TRY(c->ensure(B.dd_bins, (size_t)nb * (DD_BINS_MAX + 1) * 4));
+        GKC_TRY(c->ensure(B.dd_lg, (size_t)nb * 4)); GKC_TRY(c->ensure(B.dd_off, ((size_t)Pn + 1) * 8)); GKC_TRY(c->ensure(B.dd_ptr, 8));
+        const void*& arena_p = dd_arena_h; arena_p = B.dd_arena.p;
+        GKC_HIP(c, hipMemcpyAsync(B.dd_base.p, base.data(), (size_t)(nb + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
+        GKC_HIP(c, hipMemcpyAsync(B.dd_off.p, off.data(), ((size_t)Pn + 1) * 8, hipMemcpyHostToDevice, cur_stream(c)));
+        GKC_HIP(c, hipMemcpyAsync(B.dd_ptr.p, &arena_p, 8, hipMemcpyHostToDevice, cur_stream(c)));
+        DedupeTables DT{ (uint32_t*)B.dd_bins.p, (uint32_t*)B.dd_lg.p };
+        {   ScopedTimer tm(c, "dedupe_bin");
+            hipLaunchKernelGGL((k_dedupe_bin<RW>), dim3(std::min(nb, 512u)), dim3(DD_THREADS), 0, cur_stream(c), (const PartDesc*)B.pd.p, segs, k, (const uint64_t*)B.dd_base.p,
+                               (uint64_t*)B.dd_arena.p, DT, nb, misc + 5);
         }
+        GKC_TRY(c->ensure(B.dd_end, (size_t)Pn * 8));
+        ScopedTimer tm(c, "dedupe_sort");
+        hipLaunchKernelGGL((k_dedupe_sort<RW>), dim3(std::min(nb, 512u)), dim3(DDCap<RW>::WAVES * 64), 0, cur_stream(c), (uint64_t*)B.dd_arena.p, (const uint64_t*)B.dd_base.p, DT, (const PartDesc*)B.pd.p,
+                           (uint64_t*)B.dd_end.p, nb, misc + 44, dd_totals, L.wcap);
+        GKC_HIP(c, hipGetLastError());
+        segs_b.rec = (const uint8_t* const*)B.dd_ptr.p; segs_b.rec_off = (const uint64_t*)B.dd_off.p; segs_b.n_seg = 1; segs_b.rec_end = (const uint64_t*)B.dd_end.p;
+        return GKC_OK;
     }
-    {   ScopedTimer tm(c, "expand_count");
-        hipLaunchKernelGGL((k_expand_count<KW, RW>), dim3(nv), dim3(EXPAND_THREADS), 0, cur_stream(c), d_entries, segs_b, k,
-                           (uint64_t*)B.b_start.p, (uint32_t*)B.b_n.p, (uint8_t*)B.b_cons.p, T, (const uint32_t*)B.order.p, nv, misc + 7, drop, ST);
-        CB_HIP(hipGetLastError());
-    }
-    {   ScopedTimer tm(c, "expand_scatter");
+
+    // --- records -> keys: count per sub-bucket (which decides the tier of every sub-bucket), then scatter
+    int expand()
+    {
+        const uint32_t nv = L.nv, wb = L.wb;
+        {   ScopedTimer tm(c, "expand_count");
+            hipLaunchKernelGGL((k_expand_count<KW, RW>), dim3(nv), dim3(EXPAND_THREADS), 0, cur_stream(c), d_entries, segs_b, k,
+                               (uint64_t*)B.b_start.p, (uint32_t*)B.b_n.p, (uint8_t*)B.b_cons.p, T, (const uint32_t*)B.order.p, nv, misc + 7, L.drop, ST);
+            GKC_HIP(c, hipGetLastError());
+        }
+        ScopedTimer tm(c, "expand_scatter");
         // The scatter is bound by the write requests the whole chip retires, not by its CUs (tools/scatter_bench: 63-127 workgroups write MORE than 254), and the
         // other Stage-B lane's kernel wants CUs: the launch takes 11/16 of them (persistent workgroups, partitions handed out largest first by a ticket).
         // Measured, two lanes, 1e8 reads: one workgroup per partition 266-273 ms per step, 160-192 workgroups 249-251, 128: 252, 96: 256.
-        const uint32_t scatter_wgs = gkc_tun().scatter_wgs;
+        const uint32_t scatter_wgs = tun.scatter_wgs;
         if constexpr (KW == 1) {
             const size_t comb = (size_t)PAIR_THREADS * 8 + 16;                                            // 64 pairing words per wave (same-address relief)
-            const size_t lds_max = (size_t)MAX_SUB * 12 + comb, lds = ((size_t)12 << max_bits_b) + comb;          // parking slots + cursors of the batch's largest sub-bucket count
+            const size_t lds_max = (size_t)MAX_SUB * 12 + comb, lds = ((size_t)12 << L.max_bits_b) + comb;        // parking slots + cursors of the batch's largest sub-bucket count
             static std::once_flag once; std::call_once(once, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_expand_scatter_pair), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max); });
             hipLaunchKernelGGL(k_expand_scatter_pair, dim3(std::min(nv, scatter_wgs)), dim3(PAIR_THREADS), lds, cur_stream(c), d_entries, segs_b, k,
                                (const uint64_t*)B.b_start.p, (uint64_t*)B.keysA.p, (const uint32_t*)B.order.p, nv, misc + 6, wb, ST);
@@ -2352,58 +2421,52 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
             hipLaunchKernelGGL(k_expand_scatter_pair2, dim3(std::min(nv, scatter_wgs)), dim3(PAIR_THREADS), lds, cur_stream(c), d_entries, segs_b, k,
                                (const uint64_t*)B.b_start.p, (u128*)B.keysA.p, (const uint32_t*)B.order.p, nv, misc + 6, wb, ST);
         }
-        CB_HIP(hipGetLastError());
+        GKC_HIP(c, hipGetLastError());
+        return GKC_OK;
     }
-    SortOut O{};
-    O.cnt8 = (uint8_t*)B.cnt8.p; O.cnt32 = (uint32_t*)B.cnt.p; O.histo = c->histo_of(pass); O.histo_max = c->histo_max;
-    O.nd = (uint32_t*)B.nd.p; O.ns = all_solid ? (uint32_t*)B.nd.p : (uint32_t*)B.ns.p; O.amin = c->amin; O.amax = c->amax; O.all_solid = all_solid ? 1u : 0u;
 
-    O.wb = wb;
-    // --- the sort tiers, back to back: which sub-bucket goes where was decided by k_expand_count; no host round trip until the totals below
-    // every bucket's keys share their top min_bits1 bits: when the rest fits a double's 52-bit mantissa the in-lane exchanges run as v_min/max_f64
-    // (16-byte keys, round 4: the same tag on the key's top word — v_min/max_f64 there, selects on the low word: KTag<2>)
-    const bool tag = 2 * k + wb <= (uint32_t)KTagBits<KW>::value + min_bits1 && !gkc_tun().no_f64;
-    constexpr bool FT = true;
-    key_t* const keysA = (key_t*)B.keysA.p; key_t* const keysB = (key_t*)B.keysB.p;
-    const uint64_t* const bs = (const uint64_t*)B.b_start.p; const uint32_t* const bn = (const uint32_t*)B.b_n.p; const uint8_t* const bc = (const uint8_t*)B.b_cons.p;
-    {   ScopedTimer tm(c, "bucket_sort");
-        const uint64_t sgrid_env = 256 * 32;
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_sub + 3) / 4, sgrid_env));
-        if (tag) hipLaunchKernelGGL((k_wave_sort<KW, FT>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (uint32_t)n_sub, O);
-        else hipLaunchKernelGGL((k_wave_sort<KW, false>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (uint32_t)n_sub, O);
-        CB_HIP(hipGetLastError());
+    // --- the sort tiers, back to back: which sub-bucket goes where was decided by k_expand_count; no host round trip until the totals of prefix()
+    int sort_tiers()
+    {
+        const bool tag = L.tag; const uint64_t list_cap = L.list_cap;
+        {   ScopedTimer tm(c, "bucket_sort");
+            const uint64_t sgrid_env = 256 * 32;
+            const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_sub + 3) / 4, sgrid_env));
+            if (tag) hipLaunchKernelGGL((k_wave_sort<KW, FT>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (uint32_t)n_sub, O);
+            else hipLaunchKernelGGL((k_wave_sort<KW, false>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (uint32_t)n_sub, O);
+            GKC_HIP(c, hipGetLastError());
+        }
+        {   ScopedTimer tm(c, "bucket_sort_big");                 // up to 2x the first tier: double-size wave network
+            const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((list_cap + 3) / 4, 256 * 16));
+            constexpr int KB = WaveCapHuge<KW>::KPL;
+            if (tag) hipLaunchKernelGGL((k_wave_sort_big<KW, FT, KB>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.big_list, (const uint32_t*)T.big_count, O);
+            else hipLaunchKernelGGL((k_wave_sort_big<KW, false, KB>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.big_list, (const uint32_t*)T.big_count, O);
+            GKC_HIP(c, hipGetLastError());
+        }
+        {   ScopedTimer tm(c, "bucket_sort_wg");                  // beyond one wave: workgroups of 4 waves, merges across waves through LDS
+            static std::once_flag once;
+            std::call_once(once, [&] {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wg_sort<KW, 4, K1, FT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C1 * sizeof(key_t)));
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wg_sort<KW, 4, K1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C1 * sizeof(key_t)));
+            });
+            const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(list_cap, 256 * 4));
+            if (tag) hipLaunchKernelGGL((k_wg_sort<KW, 4, K1, FT>), dim3(grid), dim3(256), C1 * sizeof(key_t), cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.wg_list, (const uint32_t*)T.wg_count, O);
+            else hipLaunchKernelGGL((k_wg_sort<KW, 4, K1, false>), dim3(grid), dim3(256), C1 * sizeof(key_t), cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.wg_list, (const uint32_t*)T.wg_count, O);
+            GKC_HIP(c, hipGetLastError());
+        }
+        return GKC_OK;
     }
-    {   ScopedTimer tm(c, "bucket_sort_big");                 // up to 2x the first tier: double-size wave network
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((list_cap + 3) / 4, 256 * 16));
-        constexpr int KB = WaveCapHuge<KW>::KPL;
-        if (tag) hipLaunchKernelGGL((k_wave_sort_big<KW, FT, KB>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.big_list, (const uint32_t*)T.big_count, O);
-        else hipLaunchKernelGGL((k_wave_sort_big<KW, false, KB>), dim3(grid), dim3(SORT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.big_list, (const uint32_t*)T.big_count, O);
-        CB_HIP(hipGetLastError());
-    }
-    {   ScopedTimer tm(c, "bucket_sort_wg");                  // beyond one wave: workgroups of 4 waves, merges across waves through LDS
-        static std::once_flag once;
-        std::call_once(once, [&] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wg_sort<KW, 4, K1, FT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C1 * sizeof(key_t)));
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_wg_sort<KW, 4, K1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(C1 * sizeof(key_t)));
-        });
-        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(list_cap, 256 * 4));
-        if (tag) hipLaunchKernelGGL((k_wg_sort<KW, 4, K1, FT>), dim3(grid), dim3(256), C1 * sizeof(key_t), cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.wg_list, (const uint32_t*)T.wg_count, O);
-        else hipLaunchKernelGGL((k_wg_sort<KW, 4, K1, false>), dim3(grid), dim3(256), C1 * sizeof(key_t), cur_stream(c), (const key_t*)keysA, keysA, bs, bn, (const uint32_t*)T.wg_list, (const uint32_t*)T.wg_count, O);
-        CB_HIP(hipGetLastError());
-    }
+
     // split levels: level 1 takes the split list, level l > 1 the queue level l-1 filled; queue buffers alternate, the counters are used cyclically. Every level
     // is followed by the launch that sorts the pieces it listed (<= keys / 64 of them per level: the list is reused)
-    const uint32_t deep_bits = gkc_tun().deep_bits;   // tests: few bits per level force many levels
-    const uint64_t sort_cap = n_slots / (CAP1 / 4) + list_cap + 64 + (uint64_t)GIANT_MAX * MAX_SUB;     // an item of n keys lists <= 2 n / (cap1 / 2) + 1 runs and pieces
-    CB_TRY(c->ensure(B.sitems, (size_t)sort_cap * sizeof(SortItem)));
-    const unsigned deep_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(list_cap, 256 * 8));
-    auto counters_of = [&](int level) -> uint32_t* { return misc + 8 + 4 * (level % DEEP_COUNTERS); };     // [0] items for the next level [1] pieces to sort [2] ticket
-    auto launch_deep = [&](int level) -> int {
-        const uint32_t* roots = level == 1 ? (const uint32_t*)T.split_list : nullptr;
-        const uint32_t* n_in = level == 1 ? (const uint32_t*)T.split_count : (const uint32_t*)counters_of(level - 1);
-        const DeepItem* q_in = (const DeepItem*)B.q[(level - 1) & 1].p; DeepItem* q_out = (DeepItem*)B.q[level & 1].p;
-        uint32_t* cn = counters_of(level);
-        if (level > DEEP_FIXED) CB_HIP(hipMemsetAsync(cn, 0, 16, cur_stream(c)));                         // (the first ones were cleared with the whole block)
+    int launch_deep(int lv)
+    {
+        const uint32_t wb = L.wb;
+        const uint32_t* roots = lv == 1 ? (const uint32_t*)T.split_list : nullptr;
+        const uint32_t* n_in = lv == 1 ? (const uint32_t*)T.split_count : (const uint32_t*)counters_of(lv - 1);
+        const DeepItem* q_in = (const DeepItem*)B.q[(lv - 1) & 1].p; DeepItem* q_out = (DeepItem*)B.q[lv & 1].p;
+        uint32_t* cn = counters_of(lv);
+        if (lv > DEEP_FIXED) GKC_HIP(c, hipMemsetAsync(cn, 0, 16, cur_stream(c)));                        // (the first ones were cleared with the whole block)
         const uint32_t bits_small = std::min<uint32_t>(deep_bits, DEEP_SMALL_BITS), bits_large = std::min<uint32_t>(deep_bits, (uint32_t)MAX_SUB_BITS);
         static std::once_flag once_deep; std::call_once(once_deep, [&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_deep_split<KW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)8 << MAX_SUB_BITS)); });
         hipLaunchKernelGGL((k_deep_split<KW>), dim3(deep_grid), dim3(DEEP_THREADS), (size_t)8 << bits_small, cur_stream(c), keysA, keysB, roots, bs, bn, bc, q_in, n_in, cn + 2, q_out, cn + 0,
@@ -2411,40 +2474,47 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
         hipLaunchKernelGGL((k_deep_split<KW>), dim3(std::min(deep_grid, 512u)), dim3(DEEP_THREADS), (size_t)8 << bits_large, cur_stream(c), keysA, keysB, roots, bs, bn, bc, q_in, n_in, cn + 3, q_out, cn + 0,
                            (SortItem*)B.sitems.p, cn + 1, 2 * k + wb, bits_large, DEEP_SMALL_N, 0xFFFFFFFFu, CAP1, O);
         const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((sort_cap + 3) / 4, 256 * 8));
-        if (tag) hipLaunchKernelGGL((k_sort_items<KW, FT>), dim3(sgrid), dim3(SORT_THREADS), 0, cur_stream(c), keysA, (const key_t*)keysB, (const SortItem*)B.sitems.p, (const uint32_t*)(cn + 1), 0u, O);
+        if (L.tag) hipLaunchKernelGGL((k_sort_items<KW, FT>), dim3(sgrid), dim3(SORT_THREADS), 0, cur_stream(c), keysA, (const key_t*)keysB, (const SortItem*)B.sitems.p, (const uint32_t*)(cn + 1), 0u, O);
         else hipLaunchKernelGGL((k_sort_items<KW, false>), dim3(sgrid), dim3(SORT_THREADS), 0, cur_stream(c), keysA, (const key_t*)keysB, (const SortItem*)B.sitems.p, (const uint32_t*)(cn + 1), 0u, O);
-        CB_HIP(hipGetLastError());
+        GKC_HIP(c, hipGetLastError());
         return GKC_OK;
-    };
-    {   ScopedTimer tm(c, "split_levels");
-        {   // giants first: their pieces join level 1's sort list / queue
-            const size_t gor_bytes = (size_t)GIANT_MAX * 32, tab_bytes = (size_t)GIANT_MAX * MAX_SUB * 4;
-            CB_TRY(c->ensure(B.giant, gor_bytes + 2 * tab_bytes));
-            CB_HIP(hipMemsetAsync(B.giant.p, 0, gor_bytes + tab_bytes, cur_stream(c)));                    // OR words + histograms (the cursors are written by k_giant_plan)
-            GiantTables G{ (unsigned long long*)B.giant.p, (uint32_t*)((uint8_t*)B.giant.p + gor_bytes), (uint32_t*)((uint8_t*)B.giant.p + gor_bytes + tab_bytes),
-                           (const uint32_t*)T.giant_list, (const uint32_t*)T.giant_count };
-            uint32_t* cn = counters_of(1);
-            hipLaunchKernelGGL((k_giant_or<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, G, bs, bn, (uint8_t*)B.cnt8.p, wb);
-            hipLaunchKernelGGL((k_giant_hist<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, G, bs, bn, bc, 2 * k + wb, deep_bits, wb);
-            hipLaunchKernelGGL((k_giant_plan<KW>), dim3(GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), keysA, G, bs, bn, bc, (DeepItem*)B.q[1].p, cn + 0,
-                               (SortItem*)B.sitems.p, cn + 1, 2 * k + wb, deep_bits, CAP1, O);
-            hipLaunchKernelGGL((k_giant_scatter<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysB, G, bs, bn, bc, 2 * k + wb, deep_bits, wb);
-            CB_HIP(hipGetLastError());
-        }
-        for (int level = 1; level <= DEEP_FIXED; level++) CB_TRY(launch_deep(level));
+    }
+    // giants: sub-buckets too large for one split level to take in; their pieces join level 1's sort list / queue
+    int giants()
+    {
+        const uint32_t wb = L.wb;
+        const size_t gor_bytes = (size_t)GIANT_MAX * 32, tab_bytes = (size_t)GIANT_MAX * MAX_SUB * 4;
+        GKC_TRY(c->ensure(B.giant, gor_bytes + 2 * tab_bytes));
+        GKC_HIP(c, hipMemsetAsync(B.giant.p, 0, gor_bytes + tab_bytes, cur_stream(c)));                    // OR words + histograms (the cursors are written by k_giant_plan)
+        GiantTables G{ (unsigned long long*)B.giant.p, (uint32_t*)((uint8_t*)B.giant.p + gor_bytes), (uint32_t*)((uint8_t*)B.giant.p + gor_bytes + tab_bytes),
+                       (const uint32_t*)T.giant_list, (const uint32_t*)T.giant_count };
+        uint32_t* cn = counters_of(1);
+        hipLaunchKernelGGL((k_giant_or<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, G, bs, bn, (uint8_t*)B.cnt8.p, wb);
+        hipLaunchKernelGGL((k_giant_hist<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, G, bs, bn, bc, 2 * k + wb, deep_bits, wb);
+        hipLaunchKernelGGL((k_giant_plan<KW>), dim3(GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), keysA, G, bs, bn, bc, (DeepItem*)B.q[1].p, cn + 0,
+                           (SortItem*)B.sitems.p, cn + 1, 2 * k + wb, deep_bits, CAP1, O);
+        hipLaunchKernelGGL((k_giant_scatter<KW>), dim3(GIANT_WGS, GIANT_MAX), dim3(GIANT_THREADS), 0, cur_stream(c), (const key_t*)keysA, keysB, G, bs, bn, bc, 2 * k + wb, deep_bits, wb);
+        GKC_HIP(c, hipGetLastError());
+        return GKC_OK;
+    }
+    // --- what the tiers could not sort: the giants first ("level 0"), then the split levels launched unconditionally
+    int split()
+    {
+        GKC_TRY(c->ensure(B.sitems, (size_t)sort_cap * sizeof(SortItem)));
+        ScopedTimer tm(c, "split_levels");
+        for (int lv = 0; lv <= DEEP_FIXED; lv++) GKC_TRY(lv >= 1 ? launch_deep(lv) : giants());
+        return GKC_OK;
     }
 
-    // --- dump: prefix over the per-bucket counts -> Count records
-    uint64_t total_solid = 0;
-    std::vector<uint64_t> ptot((size_t)(nb + 1) * 2);
-    {   // "compact" times the KERNELS of the dump (two intervals: the prefix kernels, the gather kernels); the fetch of the prefix tables, the wait for it and the
-        // allocation of the output block between them are host time — inside one interval they made the group look 2-3x its size wherever the host was busy (round 6)
+    // --- prefix over the per-bucket counts, fetched by the host; as long as the last split level left work: one more level, then the prefix again.
+    // "compact" times the KERNELS of the dump (two intervals: the prefix kernels here, the gather kernels of dump()); the fetch of the prefix tables, the wait for it and the
+    // allocation of the output block between them are host time — inside one interval they made the group look 2-3x its size wherever the host was busy (round 6)
+    int prefix()
+    {
         const uint32_t n_chunks = (uint32_t)((n_sub + SCAN2_CHUNK - 1) / SCAN2_CHUNK);
-        if (n_chunks > (uint32_t)SCAN2_CHUNK) { B.release(); GKC_FAIL(c, GKC_ERR_ARG, "batch too large for the sub-bucket scan"); }
-        CB_TRY(c->ensure(B.chunk, (size_t)std::max<uint32_t>(n_chunks, 1) * 16));
+        if (n_chunks > (uint32_t)SCAN2_CHUNK) GKC_FAIL(c, GKC_ERR_ARG, "batch too large for the sub-bucket scan");
+        GKC_TRY(c->ensure(B.chunk, (size_t)std::max<uint32_t>(n_chunks, 1) * 16));
         uint64_t* ca = (uint64_t*)B.chunk.p; uint64_t* cb = ca + std::max<uint32_t>(n_chunks, 1);
-        uint32_t h_misc[64];
-        int level = DEEP_FIXED;
         for (uint64_t first = 1;; first = 0) {
             {   ScopedTimer tm(c, "compact", first);
             if (n_chunks) hipLaunchKernelGGL(k_scan2_chunks, dim3(n_chunks), dim3(1024), 0, cur_stream(c), (const uint32_t*)O.nd, (const uint32_t*)O.ns, n_sub, (uint64_t*)B.off_d.p, (uint64_t*)B.off_s.p, ca, cb);
@@ -2453,53 +2523,62 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
             hipLaunchKernelGGL(k_gather_u64, dim3((nb + 1 + 255) / 256), dim3(256), 0, cur_stream(c), (const uint64_t*)B.off_d.p, (const uint64_t*)B.off_s.p,
                                (const uint64_t*)B.pidx.p, nb + 1, (uint64_t*)B.ptot.p);
             }
-            CB_HIP(hipGetLastError());
-            CB_HIP(hipMemcpyAsync(ptot.data(), B.ptot.p, (size_t)(nb + 1) * 16, hipMemcpyDeviceToHost, cur_stream(c)));
-            CB_HIP(hipMemcpyAsync(h_misc, B.misc.p, sizeof(h_misc), hipMemcpyDeviceToHost, cur_stream(c)));
-            CB_HIP(hipStreamSynchronize(cur_stream(c)));
+            GKC_HIP(c, hipGetLastError());
+            GKC_HIP(c, hipMemcpyAsync(ptot.data(), B.ptot.p, (size_t)(nb + 1) * 16, hipMemcpyDeviceToHost, cur_stream(c)));
+            GKC_HIP(c, hipMemcpyAsync(h_misc, B.misc.p, sizeof(h_misc), hipMemcpyDeviceToHost, cur_stream(c)));
+            GKC_HIP(c, hipStreamSynchronize(cur_stream(c)));
             if (h_misc[8 + 4 * (level % DEEP_COUNTERS)] == 0) break;                 // the last level launched left nothing: the counts are final
             level++;                                                               // pathological skew: one more level, then the prefix again
-            if (level > 260) { B.release(); GKC_FAIL(c, GKC_ERR_HIP, "internal error: the split levels do not terminate"); }
-            CB_TRY(launch_deep(level));
+            if (level > 260) GKC_FAIL(c, GKC_ERR_HIP, "internal error: the split levels do not terminate");
+            GKC_TRY(launch_deep(level));
         }
         { std::lock_guard<std::mutex> lk(c->mu); c->pass_stats[pass].oversize_buckets += h_misc[2]; }
-        if (dedupe) {                                                    // does merging identical records pay on this input? (it costs ~13 % of Stage B)
+        if (L.dedupe) {                                                  // does merging identical records pay on this input? (it costs ~13 % of Stage B)
             unsigned long long dd[2]; memcpy(dd, h_misc + 40, 16);
             std::lock_guard<std::mutex> lk(c->mu);
             c->dedupe_in += dd[0]; c->dedupe_out += dd[1];
             c->pass_stats[pass].dedupe_kmers_in += dd[0]; c->pass_stats[pass].dedupe_keys_out += dd[1];
-            if (dedupe_env != 1 && c->dedupe_in > 100000000ULL && (double)c->dedupe_out > 0.85 * (double)c->dedupe_in) c->dedupe_off = true;
-            if (gkc_tun().verbose) fprintf(stderr, "[gkc] dedupe: %llu k-mers in the deduplicated bins -> %llu weighted keys (%.2fx)\n", dd[0], dd[1], dd[1] ? (double)dd[0] / (double)dd[1] : 0.0);
+            if (tun.dedupe != 1 && c->dedupe_in > 100000000ULL && (double)c->dedupe_out > 0.85 * (double)c->dedupe_in) c->dedupe_off = true;
+            if (tun.verbose) fprintf(stderr, "[gkc] dedupe: %llu k-mers in the deduplicated bins -> %llu weighted keys (%.2fx)\n", dd[0], dd[1], dd[1] ? (double)dd[0] / (double)dd[1] : 0.0);
         }
-        if (gkc_tun().verbose) fprintf(stderr, "[gkc] batch of %u partitions, %llu sub-buckets: %u in the double-size tier, %u in the workgroup tier, %u split (%d levels)\n",
-                                           nb, (unsigned long long)n_sub, h_misc[0], h_misc[1], h_misc[2], level);
+        if (tun.verbose) fprintf(stderr, "[gkc] batch of %u partitions, %llu sub-buckets: %u in the double-size tier, %u in the workgroup tier, %u split (%d levels)\n",
+                                 nb, (unsigned long long)n_sub, h_misc[0], h_misc[1], h_misc[2], level);
         total_solid = ptot[2 * nb + 1];
-        constexpr int OW = (KW == 1) ? 2 : 4;
-        void* out = c->dalloc((size_t)std::max<uint64_t>(total_solid, 1) * OW * 8);
-        if (!out) { B.release(); return GKC_ERR_NOMEM; }
+        return GKC_OK;
+    }
+
+    // --- dump: the output block of the batch, Count records gathered into it
+    int dump(std::vector<void*>& outputs)
+    {
+        out = c->dalloc((size_t)std::max<uint64_t>(total_solid, 1) * OW * 8);
+        if (!out) return GKC_ERR_NOMEM;
         { std::lock_guard<std::mutex> lk(c->mu); outputs.push_back(out); }
-        if (n_sub) {
-            ScopedTimer tm(c, "compact", 0);
-            const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_sub + 255) / 256, 256 * 16));
-            hipLaunchKernelGGL((k_gather_counts<KW>), dim3(grid), dim3(GATHER_THREADS), 0, cur_stream(c), (const key_t*)keysA, (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p,
-                               bs, bn, (const uint32_t*)O.nd, (const uint64_t*)B.off_s.p, (uint32_t)n_sub, cap3, c->amin, c->amax, O.all_solid, (uint64_t*)out, bc, 2 * k - drop);
-            if (h_misc[2]) {                                                       // the split sub-buckets: records at their pieces' heads
-                const uint32_t n_roots = h_misc[2];
-                const uint64_t chunks_cap = n_slots / ROOT_CHUNK + n_roots + 1;
-                CB_TRY(c->ensure(B.rbase, ((size_t)n_roots + 1) * 4)); CB_TRY(c->ensure(B.rroot, (size_t)chunks_cap * 4)); CB_TRY(c->ensure(B.rcnt, ((size_t)chunks_cap + 1) * 4));
-                RootTables R{ (uint32_t*)B.rbase.p, (uint32_t*)B.rroot.p, (uint32_t*)B.rcnt.p, misc + 4 };
-                const unsigned rgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((chunks_cap + 3) / 4, 256 * 8));
-                hipLaunchKernelGGL(k_root_chunks, dim3(1), dim3(ROOT_THREADS), 0, cur_stream(c), (const uint32_t*)T.split_list, (const uint32_t*)T.split_count, bn, R);
-                hipLaunchKernelGGL(k_root_count, dim3(rgrid), dim3(256), 0, cur_stream(c), (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p, bs, bn, (const uint32_t*)T.split_list, R, c->amin, c->amax, O.all_solid);
-                hipLaunchKernelGGL(k_root_scan, dim3(1), dim3(ROOT_THREADS), 0, cur_stream(c), R);
-                hipLaunchKernelGGL((k_root_write<KW>), dim3(rgrid), dim3(256), 0, cur_stream(c), (const key_t*)keysA, (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p, bs, bn, (const uint32_t*)T.split_list, R,
-                                   (const uint64_t*)B.off_s.p, c->amin, c->amax, O.all_solid, (uint64_t*)out, bc, 2 * k - drop);
-            }
-            CB_HIP(hipGetLastError());
+        if (!n_sub) return GKC_OK;
+        const uint32_t drop = L.drop;
+        ScopedTimer tm(c, "compact", 0);
+        const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_sub + 255) / 256, 256 * 16));
+        hipLaunchKernelGGL((k_gather_counts<KW>), dim3(grid), dim3(GATHER_THREADS), 0, cur_stream(c), (const key_t*)keysA, (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p,
+                           bs, bn, (const uint32_t*)O.nd, (const uint64_t*)B.off_s.p, (uint32_t)n_sub, L.cap3, c->amin, c->amax, O.all_solid, (uint64_t*)out, bc, 2 * k - drop);
+        if (h_misc[2]) {                                                       // the split sub-buckets: records at their pieces' heads
+            const uint32_t n_roots = h_misc[2];
+            const uint64_t chunks_cap = n_slots / ROOT_CHUNK + n_roots + 1;
+            GKC_TRY(c->ensure(B.rbase, ((size_t)n_roots + 1) * 4)); GKC_TRY(c->ensure(B.rroot, (size_t)chunks_cap * 4)); GKC_TRY(c->ensure(B.rcnt, ((size_t)chunks_cap + 1) * 4));
+            RootTables R{ (uint32_t*)B.rbase.p, (uint32_t*)B.rroot.p, (uint32_t*)B.rcnt.p, misc + 4 };
+            const unsigned rgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((chunks_cap + 3) / 4, 256 * 8));
+            hipLaunchKernelGGL(k_root_chunks, dim3(1), dim3(ROOT_THREADS), 0, cur_stream(c), (const uint32_t*)T.split_list, (const uint32_t*)T.split_count, bn, R);
+            hipLaunchKernelGGL(k_root_count, dim3(rgrid), dim3(256), 0, cur_stream(c), (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p, bs, bn, (const uint32_t*)T.split_list, R, c->amin, c->amax, O.all_solid);
+            hipLaunchKernelGGL(k_root_scan, dim3(1), dim3(ROOT_THREADS), 0, cur_stream(c), R);
+            hipLaunchKernelGGL((k_root_write<KW>), dim3(rgrid), dim3(256), 0, cur_stream(c), (const key_t*)keysA, (const uint8_t*)B.cnt8.p, (const uint32_t*)B.cnt.p, bs, bn, (const uint32_t*)T.split_list, R,
+                               (const uint64_t*)B.off_s.p, c->amin, c->amax, O.all_solid, (uint64_t*)out, bc, 2 * k - drop);
         }
-        // streamed results: the batch's records go to the host sink on the copy stream while the lanes count the next batches — packed (7 bytes per record
-        // instead of 16, expanded in place by host threads: gkc_sink.hip) when the keys are 8 bytes
-        const uint8_t* h_base = nullptr; hipEvent_t landed = nullptr; const void* sink_batch = nullptr;
+        GKC_HIP(c, hipGetLastError());
+        return GKC_OK;
+    }
+
+    // --- streamed results: the batch's records go to the host sink on the copy stream while the lanes count the next batches — packed (7 bytes per record
+    // instead of 16, expanded in place by host threads: gkc_sink.hip) when the keys are 8 bytes. Ends with the lane's stream drained.
+    int deliver()
+    {
         bool room = false;
         if (c->sink && total_solid) {
             const uint64_t bytes = total_solid * OW * 8;
@@ -2507,26 +2586,30 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
             if (c->sink_used + bytes > c->sink_cap) c->sink_overflow = true;          // the records stay on the device (gkc_partition_counts still serves them)
             else { h_base = (const uint8_t*)c->sink + c->sink_used; c->sink_used += bytes; room = true; }
         }
-        if (room && gkc_sink_packed(c) && !gkc_sink_host_behind(c, total_solid)) {
+        if (room && gkc_sink_packed(c, tun) && !gkc_sink_host_behind(c, total_solid, tun)) {
             std::vector<uint64_t> solid_prefix(nb + 1);
             for (uint32_t i = 0; i <= nb; i++) solid_prefix[i] = ptot[2 * i + 1];
-            sink_batch = gkc_sink_send_packed(c, out, (const uint64_t*)B.ptot.p, solid_prefix, (uint8_t*)h_base);      // (synchronizes the lane's stream)
+            sink_batch = gkc_sink_send_packed(c, out, (const uint64_t*)B.ptot.p, solid_prefix, (uint8_t*)h_base, tun);      // (synchronizes the lane's stream)
         }
-        CB_HIP(hipStreamSynchronize(cur_stream(c)));
+        GKC_HIP(c, hipStreamSynchronize(cur_stream(c)));
         if (room && !sink_batch) {
             const uint64_t bytes = total_solid * OW * 8;
             std::lock_guard<std::mutex> lk(c->mu);
-            if (gkc_sink_packed(c)) {                                  // a packing context whose batch travels plain: its bytes belong to what the library queued on the link
+            if (gkc_sink_packed(c, tun)) {                             // a packing context whose batch travels plain: its bytes belong to what the library queued on the link
                 c->sink_wire_bytes += bytes;
-                if (gkc_tun().sink_debug || gkc_tun().verbose) fprintf(stderr, "[gkc sink] a batch of %llu records travels unpacked: %s\n", (unsigned long long)total_solid, gkc_sink_last_refusal());
+                if (tun.sink_debug || tun.verbose) fprintf(stderr, "[gkc sink] a batch of %llu records travels unpacked: %s\n", (unsigned long long)total_solid, gkc_sink_last_refusal());
             }
-            {
-                if (hipEventCreateWithFlags(&landed, hipEventDisableTiming) == hipSuccess &&
-                    hipMemcpyAsync((void*)h_base, out, bytes, hipMemcpyDeviceToHost, c->copy_stream) == hipSuccess &&
-                    hipEventRecord(landed, c->copy_stream) == hipSuccess) c->landed_events.push_back(landed);
-                else { (void)hipGetLastError(); if (landed) (void)hipEventDestroy(landed); landed = nullptr; h_base = nullptr; c->sink_overflow = true; }
-            }
+            if (hipEventCreateWithFlags(&landed, hipEventDisableTiming) == hipSuccess &&
+                hipMemcpyAsync((void*)h_base, out, bytes, hipMemcpyDeviceToHost, c->copy_stream) == hipSuccess &&
+                hipEventRecord(landed, c->copy_stream) == hipSuccess) c->landed_events.push_back(landed);
+            else { (void)hipGetLastError(); if (landed) (void)hipEventDestroy(landed); landed = nullptr; h_base = nullptr; c->sink_overflow = true; }
         }
+        return GKC_OK;
+    }
+
+    // --- the partitions of the batch become finished datasets of the pass
+    void publish()
+    {
         {   std::lock_guard<std::mutex> lk(c->mu);
             for (uint32_t i = 0; i < nb; i++) {
                 Dataset& D = c->datasets[(size_t)pass * c->nb_partitions + batch_parts[i]];
@@ -2539,9 +2622,68 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
         }
         c->cv_done.notify_all();
     }
-    B.release();
-#undef CB_TRY
-#undef CB_HIP
+};
+
+// One batch of consecutive partitions through Stage B, on the calling lane's stream. slots_hint: key slots the big working buffers are sized for (PassPlan).
+// (pass, segments: what this Stage B was started for — Stage A may have moved the context on to the next pass meanwhile: gkc_finish_pass_async)
+template <int KW, int RW>
+static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segment>& segments, const std::vector<uint32_t>& batch_parts, const std::vector<uint64_t>& part_keys,
+                       const SegTable& segs, std::vector<void*>& outputs, const uint64_t slots_hint, const GkcTun& tun)
+{
+    BatchLayout L; std::string err;
+    const bool dedupe_allowed = tun.dedupe != 0 && (tun.dedupe == 1 || !c->dedupe_off);       // GKC_DEDUPE 0: never, 1: always, default: until a batch shows it does not pay
+    const int rc = batch_layout<KW, RW>(c->k, batch_parts, part_keys, dedupe_allowed, tun, L, err);
+    if (rc != GKC_OK) GKC_FAIL(c, rc, "%s", err.c_str());
+    BatchRun<KW, RW> R(c, pass, tun, L, batch_parts, part_keys, segs);
+    GKC_TRY(R.upload(slots_hint));
+    GKC_TRY(R.dedupe(segments, segs));
+    GKC_TRY(R.expand());
+    GKC_TRY(R.sort_tiers());
+    GKC_TRY(R.split());
+    GKC_TRY(R.prefix());
+    GKC_TRY(R.dump(outputs));
+    GKC_TRY(R.deliver());
+    R.publish();
+    return GKC_OK;             // (R goes: its buffers return to the pool, each return waiting for the lane's stream first — DevPool::free)
+}
+
+// a pass counted again (a retry after GKC_ERR_NOMEM, or gkc_finish_pass called twice) starts from a clean slate: what the
+// batches of the failed attempt added to the histogram, to the counters and to the result list must not be counted twice
+// ... and the host sink starts over as well: the failed attempt's copies are drained, its records are overwritten. Returns the pass's (empty) list of result blocks.
+static int reset_pass_results(gkc_ctx* c, const uint32_t pass, hipStream_t lane0, std::vector<void*>** outputs)
+{
+    const uint32_t Pn = c->nb_partitions;
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    gkc_sink_reset(c);                                                        // (waits for the unpack threads and the readers of their batches: outside c->mu)
+    std::lock_guard<std::mutex> lk(c->mu);
+    *outputs = &c->pass_outputs[pass];                                        // (std::map nodes stay where they are)
+    for (void* p : **outputs) c->dfree(p);
+    (*outputs)->clear();
+    for (uint32_t p = 0; p < Pn; p++) c->datasets[(size_t)pass * Pn + p] = Dataset();
+    gkc_stats& S = c->pass_stats[pass]; S.kmers_nb_distinct = 0; S.kmers_nb_solid = 0; S.oversize_buckets = 0; S.dedupe_kmers_in = 0; S.dedupe_keys_out = 0;
+    for (hipEvent_t e : c->landed_events) (void)hipEventDestroy(e);
+    c->landed_events.clear(); c->sink_used = 0; c->sink_overflow = false;
+    GKC_HIP(c, hipMemsetAsync(c->histo_of(pass), 0, ((size_t)c->histo_max + 1) * 8, lane0));
+    return GKC_OK;
+}
+
+// device copy of the segment table (the two buffers belong to the caller: they live as long as the pass)
+static int upload_segment_table(gkc_ctx* c, const std::vector<Segment>& segments, hipStream_t lane0, DevBuf& d_recptr, DevBuf& d_recoff, SegTable& segs)
+{
+    const uint32_t Pn = c->nb_partitions, n_seg = (uint32_t)segments.size();
+    std::vector<const uint8_t*> ptrs(std::max<uint32_t>(n_seg, 1), nullptr);
+    std::vector<uint64_t> offs((size_t)std::max<uint32_t>(n_seg, 1) * (Pn + 1), 0);
+    for (uint32_t s = 0; s < n_seg; s++) {
+        ptrs[s] = (const uint8_t*)segments[s].d_records;
+        memcpy(&offs[(size_t)s * (Pn + 1)], segments[s].rec_off.data(), (size_t)(Pn + 1) * 8);
+    }
+    GKC_TRY(c->ensure(d_recptr, ptrs.size() * sizeof(void*)));
+    GKC_TRY(c->ensure(d_recoff, offs.size() * 8));
+    hipError_t e1 = hipMemcpyAsync(d_recptr.p, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, lane0);      // (on the pass's own stream: a plain hipMemcpy would
+    hipError_t e2 = hipMemcpyAsync(d_recoff.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, lane0);                  //  wait for whatever Stage A of the next pass has queued)
+    if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipStreamSynchronize(lane0);
+    if (e1 != hipSuccess || e2 != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "segment table upload failed");
+    segs = SegTable{ (const uint8_t* const*)d_recptr.p, (const uint64_t*)d_recoff.p, n_seg, Pn };
     return GKC_OK;
 }
 
@@ -2550,236 +2692,76 @@ static int count_batch(gkc_ctx* c, const uint32_t pass, const std::vector<Segmen
 // may already run Stage A of the next pass on the context's stream: nothing below reads c->pass, c->segments or stats_now().
 int gkc_count_pass(gkc_ctx* c, const uint32_t pass, const std::vector<Segment>& segments, hipStream_t lane0, double reserve_bytes)
 {
+    const GkcTun tun = gkc_tun();            // ONE snapshot for the whole pass (the callers have refreshed it): the plan, the lanes' batches and their sink calls all see the same values
     const uint32_t Pn = c->nb_partitions;
-    const uint32_t n_seg = (uint32_t)segments.size();
     c->t_stage_b0 = std::chrono::steady_clock::now();
-    {   // a pass counted again (a retry after GKC_ERR_NOMEM, or gkc_finish_pass called twice) starts from a clean slate: what the
-        // batches of the failed attempt added to the histogram, to the counters and to the result list must not be counted twice
-        std::lock_guard<std::mutex> lk(c->mu);
-        auto it = c->pass_outputs.find(pass);
-        if (it != c->pass_outputs.end()) { for (void* p : it->second) c->dfree(p); it->second.clear(); }
-        for (uint32_t p = 0; p < Pn; p++) c->datasets[(size_t)pass * Pn + p] = Dataset();
-        gkc_stats& S = c->pass_stats[pass]; S.kmers_nb_distinct = 0; S.kmers_nb_solid = 0; S.oversize_buckets = 0; S.dedupe_kmers_in = 0; S.dedupe_keys_out = 0;
-        // ... and the host sink starts over as well: the failed attempt's copies are drained, its records are overwritten
-        if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-        for (hipEvent_t e : c->landed_events) (void)hipEventDestroy(e);
-        gkc_sink_reset(c);
-        c->landed_events.clear(); c->sink_used = 0; c->sink_overflow = false;
-        GKC_HIP(c, hipMemsetAsync(c->histo_of(pass), 0, ((size_t)c->histo_max + 1) * 8, lane0));
-    }
+    std::vector<void*>* outputs_p = nullptr;
+    GKC_TRY(reset_pass_results(c, pass, lane0, &outputs_p));
+    std::vector<void*>& outputs = *outputs_p;
     std::vector<uint64_t> part_keys(Pn, 0);
     for (const Segment& s : segments) for (uint32_t p = 0; p < Pn; p++) part_keys[p] += s.nkmers[p];
-    // device copy of the segment table
-    DevBuf d_recptr, d_recoff;
-    std::vector<const uint8_t*> ptrs(std::max<uint32_t>(n_seg, 1), nullptr);
-    std::vector<uint64_t> offs((size_t)std::max<uint32_t>(n_seg, 1) * (Pn + 1), 0);
-    for (uint32_t s = 0; s < n_seg; s++) {
-        ptrs[s] = (const uint8_t*)segments[s].d_records;
-        memcpy(&offs[(size_t)s * (Pn + 1)], segments[s].rec_off.data(), (size_t)(Pn + 1) * 8);
-    }
-    GKC_TRY(c->ensure(d_recptr, ptrs.size() * sizeof(void*)));
-    int rc = c->ensure(d_recoff, offs.size() * 8);
-    if (rc != GKC_OK) { d_recptr.release(); return rc; }
-    hipError_t e1 = hipMemcpyAsync(d_recptr.p, ptrs.data(), ptrs.size() * sizeof(void*), hipMemcpyHostToDevice, lane0);      // (on the pass's own stream: a plain hipMemcpy would
-    hipError_t e2 = hipMemcpyAsync(d_recoff.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice, lane0);                  //  wait for whatever Stage A of the next pass has queued)
-    if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipStreamSynchronize(lane0);
-    if (e1 != hipSuccess || e2 != hipSuccess) { d_recptr.release(); d_recoff.release(); GKC_FAIL(c, GKC_ERR_HIP, "segment table upload failed"); }
-    SegTable segs{ (const uint8_t* const*)d_recptr.p, (const uint64_t*)d_recoff.p, n_seg, Pn };
+    DevBuf d_recptr, d_recoff; SegTable segs{};
+    GKC_TRY(upload_segment_table(c, segments, lane0, d_recptr, d_recoff, segs));
 
-    // Batches of consecutive partitions, each bounded by a key budget that stays the SAME through the pass: equal batches ask the caching
-    // allocator for the same block sizes again and again, so after the first batches no hipMalloc / hipFree happens at all (hipMalloc
-    // costs ~22 ms per GB here; re-deriving the budget from the shrinking free memory made every batch a new size and a k=63 pass, where
-    // the results take half the HBM, spent seconds in the allocator). Per key slot a batch needs the key twice (a split level uses
-    // the ping-pong buffer) and 5 B of abundance planes — its working set, returned to the pool afterwards — and leaves one Count
-    // record per SOLID distinct key resident, so the peak is at the END of the pass: all results + the last working sets.
-    //  * the budget is what the working sets may take beside the results the whole pass will leave:
-    //    (0.95 free - keys * rec * 1.05 d) / (lanes * work), d = solid records per key; capped, and cut into equal shares;
-    //  * d comes from a small probe batch the first time the memory may bind (see below) and is kept by the context;
-    //  * safety net: before every batch the commitments (finished results, the other lanes' running batches) are checked, and if the
-    //    batch does not fit the extra lanes retire and the main lane halves its batches (slow: blocks change size; never seen when
-    //    the plan holds).
-    const size_t key_bytes = c->key_words == 1 ? 8 : 16, rec_bytes = c->key_words == 1 ? 16 : 32;
-    const size_t work_per_key = 2 * key_bytes + 5;
-    // Two LANES: Stage B's kernels are bound by different things (expand: store atoms and LDS, sorts: VALU, compaction: HBM), and a single
-    // in-order stream leaves most of the chip waiting on whichever bound the current kernel has. Two host threads therefore take batches
-    // from one queue, each on its own stream (thread-local stream override, cur_stream()): measured 264 -> 229 ms for the same work.
-    const uint64_t total_keys = [&] { uint64_t t = 0; for (uint64_t v : part_keys) t += v; return t; }();
-    const uint64_t max_part = [&] { uint64_t t = 0; for (uint64_t v : part_keys) t = std::max(t, v); return t; }();
-    int lanes = gkc_tun().lanes;
-    if (lanes < 1) lanes = 1;
-    if (lanes > 4) lanes = 4;
-    if (total_keys < 50000000ULL || c->key_budget) lanes = 1;               // small inputs (and the tests' tiny forced budgets): one lane
-    bool tight = false;                                                       // memory is running out: the extra lanes retire, one lane finishes the pass
-    const double avail0 = [&] {                                              // memory this pass may use: free now + blocks parked in the caching allocator
-        size_t free_b = 0, total_b = 0;
+    // the memory plan of the pass (gkc_pass_plan.hpp): lanes, batch budget, which partitions form the next batch
+    PassPlanInputs in;
+    {   size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = (size_t)8 << 30;
-        return std::max(0.0, (double)(free_b + c->pool.cached_bytes) - reserve_bytes);      // (overlapped passes: what Stage A of the next pass will allocate beside this Stage B)
-    }();
-    const size_t cap_env = (size_t)gkc_tun().batch_keys;
-    // Few, large batches: every batch ends with the drain of ~12 kernels (the expand kernels run one 6 ms workgroup per partition) and
-    // eight host round trips; 8 -> 4 batches per 1.2e10 keys: 320 -> 304 ms. Equal shares, a whole number of batches per lane.
-    // With a host sink (streamed results) the batches are three times smaller: the first records start over PCIe sooner and the copy that is left
-    // when the last batch has been counted is shorter (1e8 reads, abundance-min 2: 431 -> ms per step with everything landed; profiles/r02_*)
-    const size_t cap_default = c->key_words == 1 ? (size_t)3200000000ULL : (size_t)1600000000ULL;
-    const size_t cap_mode = c->sink ? cap_default / 3 : cap_default;       // (a host sink: three batches per lane keep the link busy)
-    // gkc_set_batch_keys is an UPPER bound: never above the library's plan for the mode; GKC_BATCH_KEYS (developer switch) replaces the plan outright
-    const size_t cap = cap_env ? cap_env : c->batch_cap ? std::min(cap_mode, std::max<size_t>(c->batch_cap, (size_t)1 << 24)) : cap_mode;   // the same with one lane or two
-    uint64_t done_keys = 0, done_solid = 0;                                  // this pass: finished batches (keys, resident records) (guarded by plan_mu)
-    // budget for a given solid-per-key ratio d. Deterministic in (free memory rounded to GB, total keys, d rounded up to 0.05): every
-    // pass of a context plans the same sizes, so from the second pass on all blocks are parked already.
-    const double avail_q = std::floor(avail0 / 1e9) * 1e9;
-    int plan_lanes = (c->key_budget || total_keys < 50000000ULL) ? 1 : std::max(2, lanes);                 // (more than two lanes: planned for what will really run)                                  // one lane gets the same batches as two would (same blocks whichever way a pass runs) ...
-    auto plan_budget = [&](double d) -> size_t {
-        const double work = (double)plan_lanes * (double)work_per_key;
-        const double dq = std::min(1.0, std::ceil(1.05 * d / 0.05) * 0.05);
-        const double mem = (0.95 * avail_q - (double)total_keys * (double)rec_bytes * dq) / work;
-        const uint64_t bmem = mem > (double)((size_t)1 << 20) ? (uint64_t)mem : ((uint64_t)1 << 20);
-        if (c->nb_passes > 1) {
-            // several passes: every pass plans the SAME batch size — half the cap plus a rounded partition — whatever its share of the k-mers (minimizer % nb_passes
-            // does not cut them evenly: 5.2e9 and 6.8e9 keys for the two passes of 1e8 reads). Equal shares per pass gave every pass its own block sizes: the allocator was
-            // trimmed and refilled at every pass, 4 s of hipMalloc for 0.15 s of counting (tools/twopass_probe.py).
-            // (a small pass — the tests' — is one batch of its own size, rounded up to a power of two so that passes of similar size still plan alike)
-            uint64_t mp = 1; while (mp < max_part) mp <<= 1;
-            uint64_t tk = 1; while (tk < total_keys) tk <<= 1;
-            return (size_t)(std::min<uint64_t>(std::min<uint64_t>(bmem, cap / 2), tk) + mp);
+        in.avail_bytes = (double)(free_b + c->pool.cached_bytes);
+    }
+    in.reserve_bytes = reserve_bytes; in.key_words = c->key_words; in.nb_passes = c->nb_passes; in.sink = c->sink != nullptr; in.key_budget = c->key_budget; in.batch_cap = c->batch_cap;
+    in.d_hint = c->d_hint; in.last_plan_budget = c->last_plan_budget;
+    in.lanes = tun.lanes; in.batch_keys = tun.batch_keys; in.sink_first_div = tun.sink_first_div; in.pool_debug = tun.pool_debug; in.max_sub_bits = MAX_SUB_BITS; in.part_align = PART_ALIGN;
+    PassPlan plan(part_keys, in, [c] { c->pool.trim(); }, [c, pass, Pn](uint32_t p) {
+        {   std::lock_guard<std::mutex> lk(c->mu);       // (c->mu guards the datasets gkc_wait_partition looks at; the plan's own mutex only the batch plan)
+            Dataset& D = c->datasets[(size_t)pass * Pn + p];
+            D.d_counts = nullptr; D.n_solid = 0; D.n_distinct = 0; D.n_kmers = 0; D.done = true;
         }
-        const uint64_t b = std::min<uint64_t>(bmem, cap);
-        const uint64_t per_round = b * (uint64_t)plan_lanes;
-        const uint64_t rounds = std::max<uint64_t>((total_keys + per_round - 1) / per_round, 1);
-        const uint64_t share = total_keys / (rounds * (uint64_t)plan_lanes);
-        return (size_t)std::min<uint64_t>(b + max_part, share + share / 64 + max_part);           // a little over the share: no small last batch
-    };
-    size_t fixed_budget = 0;                                                 // set below, after the probe
-    bool probe_pending = false; const size_t probe_keys = (size_t)std::max<uint64_t>(total_keys / 256, 16000000ULL);
-    double inflight[4] = { 0, 0, 0, 0 };                                     // bytes each lane's running batch may still claim (working set + its results)
-    size_t last_b[4] = { 0, 0, 0, 0 };
-    auto per_key_now = [&]() -> double {
-        const double d_est = done_keys ? std::min(1.0, 1.05 * (double)done_solid / (double)done_keys) : (c->d_hint > 0 ? std::min(1.0, 1.05 * c->d_hint) : 1.0);
-        return (double)work_per_key + (double)rec_bytes * d_est;
-    };
-    auto budget_now = [&](int lane) -> size_t {                              // keys of the next batch of one lane (called under plan_mu)
-        if (c->key_budget) return c->key_budget;
-        double committed = 0; for (int l = 0; l < 4; l++) if (l != lane) committed += inflight[l];
-        const double left = 0.98 * avail0 - (double)done_solid * (double)rec_bytes - committed;      // (the plan keeps 0.95: headroom between plan and net)
-        const size_t fits = left > 0 ? (size_t)(left / per_key_now()) : 0;
-        size_t b = fixed_budget;
-        if (b > fits) {
-            if (gkc_tun().pool_debug) fprintf(stderr, "[gkc plan] lane %d: budget %.3e does not fit (%.3e): done_solid %.3e committed %.1f GB\n", lane, (double)b, (double)fits, (double)done_solid, committed / 1e9);
-            if (lanes > 1) tight = true;                                     // first the extra lanes retire ...
-            if (lane != 0) return b;
-            while (b > fits && b > ((size_t)1 << 20)) b /= 2;                // ... then the main lane's batches shrink
-            c->slots_hint = 0;                                               // (exact buffer sizes from here on)
-        }
-        if (b != last_b[lane]) {                                             // another batch size: the parked blocks have the wrong sizes, and
-            if (last_b[lane]) c->pool.trim();                                // reusing larger ones would keep exactly the memory that ran out
-            last_b[lane] = b;
-        }
-        return b;
-    };
-    std::vector<void*>* outputs_p; { std::lock_guard<std::mutex> lk(c->mu); outputs_p = &c->pass_outputs[pass]; }      // (std::map nodes stay where they are)
-    std::vector<void*>& outputs = *outputs_p;
-    std::mutex plan_mu; uint32_t next_p = 0; int first_rc = GKC_OK;
-    uint32_t lane_batches[4] = { 0, 0, 0, 0 }; uint64_t keys_left = total_keys;
-    const size_t sink_first_div = gkc_tun().sink_first_div;
-    auto carve = [&](std::vector<uint32_t>& batch, int lane) -> bool {   // next batch of consecutive partitions; false when nothing is left
-        std::lock_guard<std::mutex> lk(plan_mu);
-        batch.clear();
-        if (first_rc != GKC_OK) return false;
-        inflight[lane] = 0;
-        size_t budget = budget_now(lane);
-        if (tight && lane != 0) return false;
-        if (probe_pending) { probe_pending = false; budget = probe_keys; }      // the pass's first batch is the small probe batch, every pass (same batches, same blocks)
-        // streamed results: the link idles until the first batch has been counted and packed — the first batch of every lane is a quarter of the others (same
-        // working buffers: they are sized for the budget), the copies start ~25 ms sooner
-        // — and the last one as well: what is left when the last copy has landed is the expansion of the last batch on the host
-        // Round 6: a RAMP instead of one small batch — 1/4, 1/2 of the budget, then whole ones. Stage B makes packed records ~2.6x faster than the link takes
-        // them, so a batch twice the one before is ready before the link has drained; with one quarter batch per lane followed by whole ones (round 5) the link
-        // sat idle between the end of the two small copies and the arrival of the first whole batches (GKC_SINK_DEBUG timeline: 13 ms at 5e7 reads).
-        else if (c->sink && sink_first_div > 1 && !c->key_budget) {
-            const size_t small = std::max<size_t>(budget / 4, (size_t)1 << 20), tail = small * (size_t)lanes;      // keys kept back for the small last batches
-            const size_t ramp = sink_first_div >> std::min<uint32_t>(lane_batches[lane], 31u);                     // 4, 2, 1 (GKC_SINK_FIRST_DIV: the first divisor; measured 1/4: 483.8 ms per step, 1/8: 490.4, 1/16: 491.8; no ramp: 498.3)
-            if (ramp > 1) budget = std::max<size_t>(budget / ramp, (size_t)1 << 20);
-            else if (keys_left <= tail + small / 2) budget = small;
-            else if (keys_left < budget + tail) budget = std::max<size_t>(small, (size_t)(keys_left - tail));
-        }
-        lane_batches[lane]++;
-        uint64_t acc = 0;
-        while (next_p < Pn) {
-            const uint32_t p = next_p;
-            if (part_keys[p] == 0) {                           // nothing to count (e.g. a partition another rank owns): an empty, finished dataset
-                {   std::lock_guard<std::mutex> lk2(c->mu);       // (c->mu guards the datasets gkc_wait_partition looks at; plan_mu only the batch plan)
-                    Dataset& D = c->datasets[(size_t)pass * Pn + p];
-                    D.d_counts = nullptr; D.n_solid = 0; D.n_distinct = 0; D.n_kmers = 0; D.done = true;
-                }
-                c->cv_done.notify_all();
-                next_p++; continue;
-            }
-            if (!batch.empty() && acc + part_keys[p] > budget) break;
-            batch.push_back(p); acc += part_keys[p]; next_p++;
-        }
-        inflight[lane] = (double)acc * per_key_now();
-        keys_left -= std::min<uint64_t>(keys_left, acc);
-        return !batch.empty();
+        c->cv_done.notify_all();
+    });
+    // one batch on the calling thread's stream; keys / solid: what it counted
+    auto run_batch = [&](const std::vector<uint32_t>& batch, uint64_t& keys, uint64_t& solid) -> int {
+        const uint64_t hint = plan.slots_hint();
+        const int r = (c->key_words == 1) ? count_batch<1, 2>(c, pass, segments, batch, part_keys, segs, outputs, hint, tun) : count_batch<2, 4>(c, pass, segments, batch, part_keys, segs, outputs, hint, tun);
+        keys = 0; solid = 0;
+        if (r == GKC_OK) for (uint32_t p : batch) { const Dataset& D = c->datasets[(size_t)pass * Pn + p]; keys += D.n_kmers; solid += D.n_solid; }
+        return r;
     };
     auto lane_main = [&](hipStream_t st, int lane) {
         (void)hipSetDevice(c->device);
         const hipStream_t tl_before = tl_stream_;
         tl_stream_ = st;
-        std::vector<uint32_t> batch;
-        while (carve(batch, lane)) {
-            const int r = (c->key_words == 1) ? count_batch<1, 2>(c, pass, segments, batch, part_keys, segs, outputs) : count_batch<2, 4>(c, pass, segments, batch, part_keys, segs, outputs);
-            std::lock_guard<std::mutex> lk(plan_mu);
-            inflight[lane] = 0;
-            if (r != GKC_OK) { if (first_rc == GKC_OK) first_rc = r; break; }
-            for (uint32_t p : batch) { const Dataset& D = c->datasets[(size_t)pass * Pn + p]; done_keys += D.n_kmers; done_solid += D.n_solid; }
+        std::vector<uint32_t> batch; uint64_t keys, solid;
+        while (plan.carve(batch, lane)) {
+            const int r = run_batch(batch, keys, solid);
+            if (r != GKC_OK) { plan.failed(lane, r); break; }
+            plan.finished(lane, keys, solid);
         }
         (void)hipStreamSynchronize(st);
         tl_stream_ = tl_before;
     };
     (void)hipStreamSynchronize(lane0);                                       // the table uploads (and, in line, Stage A on the same stream) are complete before the lanes start
-    // d not known yet and the memory may bind: count a small PROBE batch first (the first partitions holding ~0.4 % of the keys) and take
-    // its ratio. The context keeps that first estimate (until the configuration changes), so every later pass plans the same sizes.
-    // In later passes the same small batch is simply the first one in the queue (it runs beside the other lane's first batch).
-    probe_pending = !c->key_budget && plan_budget(1.0) < plan_budget(1e-9);
-    if (probe_pending && c->d_hint <= 0) {
-        std::vector<uint32_t> batch;
-        fixed_budget = probe_keys; c->slots_hint = 0;
-        if (carve(batch, 0)) {
-            const int r = (c->key_words == 1) ? count_batch<1, 2>(c, pass, segments, batch, part_keys, segs, outputs) : count_batch<2, 4>(c, pass, segments, batch, part_keys, segs, outputs);
-            inflight[0] = 0; last_b[0] = 0;
-            if (r != GKC_OK) { d_recptr.release(); d_recoff.release(); return r; }
-            for (uint32_t p : batch) { const Dataset& D = c->datasets[(size_t)pass * Pn + p]; done_keys += D.n_kmers; done_solid += D.n_solid; }
-            if (done_keys) c->d_hint = std::max(1e-6, (double)done_solid / (double)done_keys);
+    if (plan.probe_wanted()) {                                               // solid records per key not known yet and the memory may bind: a small batch first, counted on its own
+        std::vector<uint32_t> batch; uint64_t keys, solid;
+        if (plan.carve_probe(batch)) {
+            GKC_TRY(run_batch(batch, keys, solid));
+            plan.probe_finished(keys, solid);
         }
     }
-    fixed_budget = c->d_hint > 0 ? plan_budget(c->d_hint) : plan_budget(1.0);   // without a ratio the memory does not bind even at d = 1
-    if (gkc_tun().pool_debug) fprintf(stderr, "[gkc plan] avail %.1f GB, keys %.3e, d_hint %.4f, lanes %d, budget %.3e\n", avail0 / 1e9, (double)total_keys, c->d_hint, lanes, (double)fixed_budget);
-    // another batch size than the last pass planned (another input, a host sink set or dropped, another solidity ratio): the blocks parked in the allocator have the
-    // wrong sizes — keeping them would make every new block a failed hipMalloc followed by frees, one parked block at a time (seen: 1.5 s for a 0.26 s pass)
-    if (c->last_plan_budget && (fixed_budget > c->last_plan_budget + c->last_plan_budget / 10 || fixed_budget + fixed_budget / 10 < c->last_plan_budget)) c->pool.trim();      // (the allocator reuses a block up to 25 % larger than asked)
-    c->last_plan_budget = fixed_budget;
-    if (!c->key_budget && fixed_budget < 250000000ULL) {                       // ... unless there is little room: one lane, larger batches
-        lanes = 1; plan_lanes = 1; fixed_budget = c->d_hint > 0 ? plan_budget(c->d_hint) : plan_budget(1.0);
-    }
-    {   uint64_t nonempty = 0; for (uint64_t v : part_keys) nonempty += v != 0;
-        const uint64_t avg_part = std::max<uint64_t>(total_keys / std::max<uint64_t>(nonempty, 1), 1);
-        const uint64_t hint = (uint64_t)fixed_budget + ((uint64_t)fixed_budget / avg_part + 2) * ((3ull << MAX_SUB_BITS) + PART_ALIGN);
-        c->slots_hint = c->key_budget ? 0 : (hint + PART_ALIGN - 1) / PART_ALIGN * PART_ALIGN;
-    }
-    for (int l = 1; l < lanes; l++)
-        if (!c->lane_streams[l - 1] && hipStreamCreateWithFlags(&c->lane_streams[l - 1], hipStreamNonBlocking) != hipSuccess) { c->lane_streams[l - 1] = nullptr; lanes = l; break; }
+    plan.settle();
+    c->d_hint = plan.d_hint; c->last_plan_budget = plan.last_plan_budget;
+    for (int l = 1; l < plan.lanes; l++)
+        if (!c->lane_streams[l - 1] && hipStreamCreateWithFlags(&c->lane_streams[l - 1], hipStreamNonBlocking) != hipSuccess) { c->lane_streams[l - 1] = nullptr; plan.lanes = l; break; }
     {
         std::vector<std::thread> extra;
-        for (int l = 1; l < lanes; l++) extra.emplace_back(lane_main, c->lane_streams[l - 1], l);
+        for (int l = 1; l < plan.lanes; l++) extra.emplace_back(lane_main, c->lane_streams[l - 1], l);
         lane_main(lane0, 0);
         for (auto& t : extra) t.join();
     }
-    rc = first_rc;
     c->cv_done.notify_all();
-    if (gkc_tun().pool_debug) fprintf(stderr, "[gkc pool] mallocs %llu failed %llu trims %llu, %.1f ms in hipMalloc, cached %.2f GB\n", (unsigned long long)c->pool.n_malloc,
-                                          (unsigned long long)c->pool.n_fail, (unsigned long long)c->pool.n_trim, c->pool.malloc_ms, (double)c->pool.cached_bytes / 1e9);
-    d_recptr.release(); d_recoff.release();
-    return rc;
+    if (tun.pool_debug) fprintf(stderr, "[gkc pool] mallocs %llu failed %llu trims %llu, %.1f ms in hipMalloc, cached %.2f GB\n", (unsigned long long)c->pool.n_malloc,
+                                (unsigned long long)c->pool.n_fail, (unsigned long long)c->pool.n_trim, c->pool.malloc_ms, (double)c->pool.cached_bytes / 1e9);
+    return plan.rc();
 }
 
 // explicit result checksum entry (used by the C-ABI)
@@ -2807,7 +2789,6 @@ int gkc_result_checksum_impl(gkc_ctx* c, uint64_t* checksum, uint64_t* sum_abund
     uint64_t h[2];
     hipError_t e = hipMemcpyAsync(h, d.p, 16, hipMemcpyDeviceToHost, cur_stream(c));
     if (e == hipSuccess) e = hipStreamSynchronize(cur_stream(c));
-    d.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "result checksum failed: %s", hipGetErrorString(e));
     *checksum = h[0]; *sum_abundance = h[1];
     return GKC_OK;

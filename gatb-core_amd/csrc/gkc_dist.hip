@@ -284,7 +284,6 @@ static int reduce_words(gkc_comm* m, uint64_t* d_a, uint64_t* d_b, uint64_t n_wo
         rc = gkc_comm_sendrecv(m, sends, recvs, st);
     }
     (void)hipStreamSynchronize(st);                          // scratch goes back to the pool
-    scratch.release();
     return rc;
 }
 int gkc_comm_allreduce_or_words(gkc_comm* m, uint64_t* d_words, uint64_t n_words, hipStream_t st) { return reduce_words(m, d_words, nullptr, n_words, 0, st); }
@@ -552,7 +551,6 @@ void gkc_comm_destroy(gkc_comm* m)
     if (m->xstream) (void)hipStreamSynchronize(m->xstream);
     gkc_comm_settle_timers(m);
     if (m->nccl) (void)g_rccl.CommDestroy(m->nccl);
-    m->ag_send.release(); m->ag_recv.release();
     if (m->xstream) (void)hipStreamDestroy(m->xstream);
     if (m->owned_user && m->owned_free) m->owned_free(m->owned_user);
     delete m;
@@ -718,7 +716,7 @@ int gkc_comm_loopback(gkc_ctx* c, gkc_comm* m, uint64_t n_bytes, uint64_t* misma
     DevBuf src, dst, bad;
     GKC_TRY(c->ensure(src, (size_t)n * 8 + 8));
     int rc = c->ensure(dst, (size_t)n * 8 + 8); if (rc == GKC_OK) rc = c->ensure(bad, 8);
-    if (rc != GKC_OK) { src.release(); dst.release(); return rc; }
+    if (rc != GKC_OK) return rc;
     (void)hipMemsetAsync(bad.p, 0, 8, m->xstream); (void)hipMemsetAsync(dst.p, 0, (size_t)n * 8, m->xstream);
     hipLaunchKernelGGL(k_loop_fill, dim3(1024), dim3(256), 0, m->xstream, (uint64_t*)src.p, n, 12345ull);
     (void)hipStreamSynchronize(m->xstream);
@@ -732,7 +730,6 @@ int gkc_comm_loopback(gkc_ctx* c, gkc_comm* m, uint64_t n_bytes, uint64_t* misma
         hipLaunchKernelGGL(k_loop_check, dim3(1024), dim3(256), 0, m->xstream, (const uint64_t*)dst.p, n, 12345ull, (unsigned long long*)bad.p);
         if (hipMemcpyAsync(&h, bad.p, 8, hipMemcpyDeviceToHost, m->xstream) != hipSuccess || hipStreamSynchronize(m->xstream) != hipSuccess) { c->set_error(GKC_ERR_HIP, "loopback check failed"); rc = GKC_ERR_HIP; }
     }
-    src.release(); dst.release(); bad.release();
     *mismatches = h;
     return rc;
 }
@@ -777,7 +774,6 @@ int gkc_comm_selftest(gkc_ctx* c, gkc_comm* m, uint64_t n_bytes, uint64_t* misma
         }
         if (hipMemcpyAsync(&h, bad.p, 8, hipMemcpyDeviceToHost, m->xstream) != hipSuccess || hipStreamSynchronize(m->xstream) != hipSuccess) { c->set_error(GKC_ERR_HIP, "self-test check failed"); rc = GKC_ERR_HIP; }
     }
-    src.release(); dst.release(); bad.release();
     *mismatches = h;
     return gkc_comm_agree(m, rc != GKC_OK ? rc : (h ? GKC_ERR_HIP : GKC_OK), "gkc_comm_selftest");      // one rank seeing garbage fails every rank
 }

@@ -321,8 +321,6 @@ int gkc_fastx_parse_device(gkc_ctx* c, const char* d_text, uint64_t n, int final
 
     const uint64_t n_tiles = (n + FX_TILE - 1) / FX_TILE;
     DevBuf tile_line0, tile_keep, scratch, d_info, d_tot, line_start, kind, rec_id;
-    struct Guard { std::vector<DevBuf*> v; ~Guard() { for (DevBuf* b : v) b->release(); } } guard;
-    guard.v = { &tile_line0, &tile_keep, &scratch, &d_info, &d_tot, &line_start, &kind, &rec_id };
     GKC_TRY(c->ensure(tile_line0, (size_t)n_tiles * 8)); GKC_TRY(c->ensure(tile_keep, (size_t)n_tiles * 8));
     GKC_TRY(c->ensure(d_info, sizeof(FxInfo))); GKC_TRY(c->ensure(d_tot, 64));
 
@@ -406,13 +404,12 @@ int gkc_push_fastx(gkc_ctx* c, const char* text, uint64_t n, int final_chunk, ui
     GKC_HIP(c, hipSetDevice(c->device));
     DevBuf dt;
     GKC_TRY(c->ensure(dt, (size_t)n + 64));
-    if (n) { hipError_t e = hipMemcpyAsync(dt.p, text, (size_t)n, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) { dt.release(); GKC_FAIL(c, GKC_ERR_HIP, "H2D copy failed: %s", hipGetErrorString(e)); } }
+    if (n) { hipError_t e = hipMemcpyAsync(dt.p, text, (size_t)n, hipMemcpyHostToDevice, c->stream); if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "H2D copy failed: %s", hipGetErrorString(e)); }
     char* db = nullptr; uint64_t* dof = nullptr; uint64_t nr = 0, nb = 0;
     int rc = gkc_fastx_parse_device(c, (const char*)dt.p, n, final_chunk, &db, &dof, &nr, &nb, consumed);
     if (rc == GKC_OK && nr) rc = gkc_push_reads_device(c, db, dof, nr, nb);
     (void)hipStreamSynchronize(c->stream);
     if (db) c->dfree(db);
     if (dof) c->dfree(dof);
-    dt.release();
     return rc;
 }

@@ -321,7 +321,7 @@ int ms_scan(gkc_ctx* c, uint64_t* a, uint64_t n, uint64_t* d_total, DevBuf& scra
     GKC_TRY(c->ensure(scratch, (size_t)std::max<uint64_t>(n_chunks, 1) * 8));
     if (n_chunks) hipLaunchKernelGGL(k_ms_chunks, dim3((unsigned)n_chunks), dim3(1024), 0, c->stream, a, n, (uint64_t*)scratch.p);
     if (n_chunks <= (uint64_t)MS_CHUNK) hipLaunchKernelGGL(k_ms_totals, dim3(1), dim3(1024), 0, c->stream, (uint64_t*)scratch.p, (uint32_t)n_chunks, d_total);
-    else { DevBuf deeper; int rc = ms_scan(c, (uint64_t*)scratch.p, n_chunks, d_total, deeper); (void)hipStreamSynchronize(c->stream); deeper.release(); if (rc != GKC_OK) return rc; }
+    else { DevBuf deeper; int rc = ms_scan(c, (uint64_t*)scratch.p, n_chunks, d_total, deeper); (void)hipStreamSynchronize(c->stream); if (rc != GKC_OK) return rc; }
     if (n_chunks) hipLaunchKernelGGL(k_ms_add, dim3((unsigned)n_chunks), dim3(1024), 0, c->stream, a, n, (const uint64_t*)scratch.p);
     GKC_HIP(c, hipGetLastError());
     return GKC_OK;
@@ -366,7 +366,6 @@ static int mphf_build_from_list(gkc_ctx* c, gkc_mphf* m, DevBuf& keysA, uint64_t
     GKC_TRY(c->ensure(m->bits, (size_t)words * 8)); GKC_TRY(c->ensure(m->ranks, (size_t)nr * 8));
     GKC_HIP(c, hipMemsetAsync(m->bits.p, 0, (size_t)words * 8, c->stream));
     DevBuf keysB, coll, flag, scratch, d_tot, r_wg, r_off, r_items;
-    struct Guard { std::vector<DevBuf*> v; ~Guard() { for (DevBuf* b : v) b->release(); } } guard; guard.v = { &keysB, &coll, &flag, &scratch, &d_tot, &r_wg, &r_off, &r_items };
     GKC_TRY(c->ensure(coll, (size_t)m->nchar[0] * 8)); GKC_TRY(c->ensure(d_tot, 64));
     DevBuf* cur = &keysA; DevBuf* nxt = &keysB;
     bool used_regions = false;
@@ -487,7 +486,7 @@ static int mphf_build_from_list(gkc_ctx* c, gkc_mphf* m, DevBuf& keysA, uint64_t
 
 extern "C" {
 
-void gkc_mphf_destroy(gkc_mphf* m) { if (m) { gkc_ctx* c = m->ctx; m->bits.release(); m->ranks.release(); m->final_keys.release(); delete m; gkc_ctx_child_release(c); } }
+void gkc_mphf_destroy(gkc_mphf* m) { if (m) { gkc_ctx* c = m->ctx; delete m; gkc_ctx_child_release(c); } }
 uint64_t gkc_mphf_size(const gkc_mphf* m) { return m ? m->nelem : 0; }
 
 static int mphf_build_arrays(gkc_ctx* c, const std::vector<std::pair<const uint8_t*, uint64_t>>& segs, uint32_t stride, uint32_t k, bool on_host, gkc_mphf** out, gkc_comm* comm = nullptr)
@@ -522,7 +521,7 @@ static int mphf_build_arrays(gkc_ctx* c, const std::vector<std::pair<const uint8
     if (rc != GKC_MPHF_REBUILD_ORDERED) break;
   }
     (void)hipStreamSynchronize(c->stream);
-    keys.release(); tmp.release();
+    keys.release(); tmp.release();                       // handed back early: a failed build may drop the last reference to a closed context below
     if (rc != GKC_OK) { gkc_mphf_destroy(m); return rc; }
     *out = m;
     return GKC_OK;
@@ -582,8 +581,7 @@ int gkc_mphf_lookup(gkc_mphf* m, const void* keys, uint64_t n, uint32_t stride, 
     const uint32_t need = m->wide ? 16 : 8;
     if (stride < need || stride % 8) GKC_FAIL(c, GKC_ERR_ARG, "stride %u invalid", stride);
     DevBuf dk, dc; GKC_TRY(c->ensure(dk, (size_t)n * stride));
-    int rc = c->ensure(dc, (size_t)n * 8);
-    if (rc != GKC_OK) { dk.release(); return rc; }
+    GKC_TRY(c->ensure(dc, (size_t)n * 8));
     hipError_t e = hipMemcpyAsync(dk.p, keys, (size_t)n * stride, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         ScopedTimer tm(c, "mphf_lookup");
@@ -594,7 +592,6 @@ int gkc_mphf_lookup(gkc_mphf* m, const void* keys, uint64_t n, uint32_t stride, 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(codes, dc.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dk.release(); dc.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "MPHF lookup failed: %s", hipGetErrorString(e));
     return GKC_OK;
 }
@@ -657,7 +654,7 @@ static int abundance_map_impl(gkc_mphf* m, gkc_ctx* c, gkc_comm* comm, uint8_t* 
     const size_t map_bytes = ((size_t)m->nelem + 15) / 8 * 8;      // whole 8-byte words (the cross-rank OR works on words)
     DevBuf dmap, dst; GKC_TRY(c->ensure(dmap, map_bytes));
     int rc = c->ensure(dst, 16);
-    if (rc != GKC_OK) { dmap.release(); return rc; }
+    if (rc != GKC_OK) return rc;
     hipError_t e = hipMemsetAsync(dmap.p, 0, map_bytes, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(dst.p, 0, 16, c->stream);
     const uint32_t stride = c->key_words == 1 ? 16 : 32;
@@ -679,12 +676,11 @@ static int abundance_map_impl(gkc_mphf* m, gkc_ctx* c, gkc_comm* comm, uint8_t* 
     unsigned long long st[2] = {0, 0};
     if (e == hipSuccess && comm) {          // every cell is written by exactly one rank (zero elsewhere): OR over the ranks = the whole map
         rc = gkc_comm_allreduce_or_words(comm, (uint64_t*)dmap.p, (uint64_t)(map_bytes / 8), c->stream);
-        if (rc != GKC_OK) { dmap.release(); dst.release(); return rc; }
+        if (rc != GKC_OK) return rc;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dmap.p, (size_t)m->nelem, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st, dst.p, 16, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dmap.release(); dst.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "abundance map failed: %s", hipGetErrorString(e));
     if (!comm && st[1]) GKC_FAIL(c, GKC_ERR_ARG, "MPHF check: value out of bounds (%llu k-mers are not keys of this MPHF)", st[1]);      // MPHFAlgorithm.cpp:247
     if (comm) {                                                    // (several ranks: the counters are summed first, so that all ranks fail together)                                                    // counters over all ranks

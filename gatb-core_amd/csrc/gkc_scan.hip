@@ -909,7 +909,6 @@ int gkc_scan_push(gkc_ctx* c, const char* d_bases, const uint64_t* d_offsets, ui
         Segment fine; fine.rec_off.assign(Pfine + 1, 0); fine.nkmers.assign(Pfine, 0); fine.owned = true;
         if (total) {
             DevBuf d_fid, d_cnt, d_coff;
-            struct Guard { DevBuf *a, *b, *cc; ~Guard() { a->release(); b->release(); cc->release(); } } guard{&d_fid, &d_cnt, &d_coff};
             if (!stash) GKC_TRY(c->ensure(d_fid, (size_t)total));
             GKC_TRY(c->ensure(d_cnt, ((size_t)2 * Pfine + 2) * 8)); GKC_TRY(c->ensure(d_coff, ((size_t)Pn + 1) * 8));
             GKC_HIP(c, hipMemsetAsync(d_cnt.p, 0, ((size_t)2 * Pfine + 2) * 8, c->stream));
@@ -984,7 +983,6 @@ int gkc_scan_sample(gkc_ctx* c, const char* d_bases, const uint64_t* d_offsets, 
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) for (uint64_t i = 0; i < nm; i++) { h_superkmers[i] += a[i]; h_kmers[i] += b[i]; }
     }
-    cnt.release();
     if (rc != GKC_OK) return rc;
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "minimizer sampling failed: %s", hipGetErrorString(e));
     return GKC_OK;
@@ -1090,7 +1088,6 @@ int gkc_scan_count_mmers(gkc_ctx* c, uint32_t m, const char* d_bases, const uint
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_counts, cnt.p, nm * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cnt.release();
     if (e != hipSuccess) GKC_FAIL(c, GKC_ERR_HIP, "m-mer counting failed: %s", hipGetErrorString(e));
     return GKC_OK;
 }
@@ -1144,7 +1141,6 @@ int gkc_scan_sample_exact(gkc_ctx* c, const char* bases, const uint64_t* offsets
 {
     const uint64_t nm = 1ULL << (2 * c->m);
     DevBuf d_stats, d_per, db, dof;
-    struct Guard { std::vector<DevBuf*> v; ~Guard() { for (DevBuf* b : v) b->release(); } } guard; guard.v = { &d_stats, &d_per, &db, &dof };
     GKC_TRY(c->ensure(d_stats, (size_t)3 * nm * 8));
     GKC_HIP(c, hipMemsetAsync(d_stats.p, 0, (size_t)3 * nm * 8, c->stream));
     ScanParams P{};

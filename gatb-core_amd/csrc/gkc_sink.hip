@@ -415,7 +415,6 @@ struct SinkBatch {
     std::chrono::steady_clock::time_point t_queued, t_ready;           // GKC_SINK_DEBUG
     double pack_ms = 0;
 };
-#define g_sink_debug (gkc_tun().sink_debug)
 
 struct gkc_unpacker {
     gkc_ctx* c = nullptr;
@@ -424,6 +423,7 @@ struct gkc_unpacker {
     std::deque<SinkBatch*> queue;                // batches whose blocks are not all taken yet, oldest first
     std::vector<SinkBatch*> all;                 // every batch of the pass (owned)
     bool stop = false;
+    bool debug = false;                          // GKC_SINK_DEBUG as it was when the sink was prepared (gkc_sink_prepare): the workers print a line per batch
     uint8_t* staging = nullptr; uint64_t staging_cap = 0, staging_used = 0;
     std::atomic<uint64_t> n_decisions{0}, n_adaptive_raw{0}, max_batch_records{0};     // batches of this context that travelled raw because the host was behind (gkc_sink_host_behind)
 
@@ -581,7 +581,7 @@ struct gkc_unpacker {
                 unpack_block(*B, g);
                 if (B->finished.fetch_add(1) + 1 == B->nblk) {
                     _mm_sfence();
-                    if (g_sink_debug) {
+                    if (debug) {
                         const auto now = std::chrono::steady_clock::now();
                         float copy_ms = -1; if (B->copy_start) (void)hipEventElapsedTime(&copy_ms, B->copy_start, B->copied);
                         const auto t00 = all.empty() ? B->t_queued : all.front()->t_queued;
@@ -652,18 +652,19 @@ static gkc_unpacker* unpacker_of(gkc_ctx* c)
 }
 
 // whether the sink of this context takes packed batches (8-byte keys; GKC_SINK_PACKED=0 keeps the plain copies)
-bool gkc_sink_packed(gkc_ctx* c)
+bool gkc_sink_packed(gkc_ctx* c, const GkcTun& tun)
 {
-    const bool off = !gkc_tun().sink_packed;
-    const bool off2 = !gkc_tun().sink_packed2;       // (16-byte keys only)
+    const bool off = !tun.sink_packed;
+    const bool off2 = !tun.sink_packed2;       // (16-byte keys only)
     return c->sink && !c->sink_raw && (c->key_words == 1 || !off2) && !off && ((uintptr_t)c->sink & 15) == 0;
 }
 
 // the staging buffer holds the packed stream of ONE pass (like the sink holds one pass of records): 7/16 of the sink + the block slack of every partition
 int gkc_sink_prepare(gkc_ctx* c)
 {
-    if (!gkc_sink_packed(c)) return GKC_OK;
+    if (!gkc_sink_packed(c, gkc_tun())) return GKC_OK;
     gkc_unpacker* U = unpacker_of(c);
+    U->debug = gkc_tun().sink_debug;
     const uint64_t want = c->key_words == 1 ? c->sink_cap / 16 * 8 + (uint64_t)c->nb_partitions * (pk_slot(8) + 8) + ((uint64_t)64 << 20)
                                             : c->sink_cap / 32 * 17 + (uint64_t)c->nb_partitions * (pk_slot(17) + 16) + ((uint64_t)64 << 20);
     if (U->staging_cap < want) {
@@ -684,7 +685,7 @@ static void pin_unpackers(gkc_unpacker* U)
     cpu_set_t set;
     if (node < 0 || !cpus_of_node(node, &set)) return;
     for (std::thread& t : U->threads) (void)pthread_setaffinity_np(t.native_handle(), sizeof(set), &set);
-    if (g_sink_debug) fprintf(stderr, "[gkc sink] %zu unpack threads on the cores of NUMA node %d (where the sink lives)\n", U->threads.size(), node);
+    if (U->debug) fprintf(stderr, "[gkc sink] %zu unpack threads on the cores of NUMA node %d (where the sink lives)\n", U->threads.size(), node);
 }
 
 // start of a pass / a pass counted again: nothing of the previous one is in flight any more
@@ -732,10 +733,10 @@ void gkc_sink_wait_batch(gkc_ctx* c, const void* batch)
 // batches. A batch queued then travels RAW instead (16 B per record on this rank's own link, no host work) — the link is busy 2.6x longer with it and the expansion
 // threads catch up: every rank balances its link against its share of the host by itself, batch by batch. The sink ends up byte for byte the same either way.
 static thread_local const char* g_sink_why = "";                   // why the last batch of this thread did not travel packed (GKC_SINK_DEBUG)
-bool gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records)
+bool gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records, const GkcTun& tun)
 {
     gkc_unpacker* U = c->unpacker;
-    if (!U || !gkc_tun().sink_adaptive) return false;
+    if (!U || !tun.sink_adaptive) return false;
     uint64_t pending = 0;
     {   std::lock_guard<std::mutex> lk(U->mu);
         for (SinkBatch* B : U->all) {
@@ -747,7 +748,7 @@ bool gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records)
     // (against the LARGEST batch of the pass so far, not this one: the small batches at the end of a ramp would otherwise see the whole batch in hand of the
     //  expansion threads as "1.5 batches behind" and travel raw — 16 instead of 6 bytes per record on the link at the very end of the step)
     uint64_t ref = U->max_batch_records.load(); if (n_records > ref) { U->max_batch_records = n_records; ref = n_records; }
-    const bool behind = gkc_tun().sink_adaptive == 2 ? (U->n_decisions++ & 1) != 0                       // (tests: packed and raw batches alternate in one pass)
+    const bool behind = tun.sink_adaptive == 2 ? (U->n_decisions++ & 1) != 0                       // (tests: packed and raw batches alternate in one pass)
                                                      : pending * PK_BLOCK > std::max<uint64_t>(ref + ref / 2, (uint64_t)1 << 22);
     if (behind) { g_sink_why = "the host is behind with the expansion (landed, unexpanded records beyond 1.5 batches): this batch travels raw"; U->n_adaptive_raw++; }
     return behind;
@@ -757,7 +758,7 @@ bool gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records)
 // h_dest = where the records belong in the sink. Runs on the calling lane's stream up to the point where the copy can be queued; returns the batch handle
 // (nullptr: not packed — no staging room, too many exceptions — the caller sends the plain records).
 const char* gkc_sink_last_refusal() { return g_sink_why; }
-void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot, const std::vector<uint64_t>& solid_prefix, uint8_t* h_dest)
+void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot, const std::vector<uint64_t>& solid_prefix, uint8_t* h_dest, const GkcTun& tun)
 {
     gkc_unpacker* U = c->unpacker;
     g_sink_why = "no staging buffer";
@@ -771,8 +772,8 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
     if (nblk == 0 || nblk >= (1ull << 31)) return nullptr;
     // width of an entry: 8 where the partitions are sparse, 7 where dense, "6" = per-block delta widths + bitmap + abundance stream (PKV) where dense at abundance-min 1
     // (most abundances are 1: sequencing errors), checked batch by batch: a batch that came out above 7 bytes per record switches the context back to 7
-    const bool no6 = !gkc_tun().sink_width6;
-    const uint64_t dense_min = gkc_tun().sink_dense ? gkc_tun().sink_dense : PK_DENSE;      // (tests: 1 = every batch is "dense")
+    const bool no6 = !tun.sink_width6;
+    const uint64_t dense_min = tun.sink_dense ? tun.sink_dense : PK_DENSE;      // (tests: 1 = every batch is "dense")
     const bool wide = c->key_words == 2;
     const bool dense = solid_prefix[nb] / std::max<uint32_t>(nb, 1) >= (wide ? std::min<uint64_t>(dense_min, PK2_DENSE) : dense_min);
     const bool pkv_ok = !no6 && !c->sink_no6 && solid_prefix[nb] < (1ull << 32);
@@ -786,7 +787,7 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
     g_sink_why = "no device memory for the packed copy";
     DevBuf d_first; if (c->ensure(d_first, (size_t)(nb + 1) * 4) != GKC_OK) return nullptr;
     uint8_t* d_packed = (uint8_t*)c->dalloc((size_t)(hdr_bytes + pay_bytes + cb_cap + (uint64_t)exc_cap * 16 + 64));
-    if (!d_packed) { d_first.release(); return nullptr; }
+    if (!d_packed) return nullptr;
     hipStream_t st = cur_stream(c);
     const auto t_pack0 = std::chrono::steady_clock::now();
     uint8_t* const d_pay = d_packed + hdr_bytes; uint8_t* const d_cb = d_pay + pay_bytes; uint8_t* const d_exc = d_cb + cb_cap;
@@ -810,7 +811,7 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
                                 (uint64_t*)d_exc, d_nexc, exc_cap);
         ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h_cnt, d_nexc, 24, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
     }
-    d_first.release();
+    d_first.release();                                   // handed back early: what follows only stages and sends the packed block
     const unsigned long long h_nexc = h_cnt[0], h_ncb = h_cnt[1];
     const uint64_t pay_used = pkv ? ((uint64_t)h_cnt[2] + 63) / 64 * 64 : pay_bytes;               // bytes of the payload that travel (and are staged)
     g_sink_why = !ok ? "pack launch failed" : "too many exceptions";
@@ -834,15 +835,15 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
         const uint64_t s0 = solid_prefix[i], s1 = solid_prefix[i + 1];
         for (uint64_t r = s0, g = blk_first[i]; r < s1; r += PK_BLOCK, g++) { B->blk_rec0[g] = r; B->blk_n[g] = (uint32_t)std::min<uint64_t>(PK_BLOCK, s1 - r); }
     }
-    if (g_sink_debug && hipEventCreate(&B->copy_start) == hipSuccess) (void)hipEventRecord(B->copy_start, c->copy_stream);
-    bool queued = hipEventCreateWithFlags(&B->copied, g_sink_debug ? hipEventDefault : hipEventDisableTiming) == hipSuccess
+    if (tun.sink_debug && hipEventCreate(&B->copy_start) == hipSuccess) (void)hipEventRecord(B->copy_start, c->copy_stream);
+    bool queued = hipEventCreateWithFlags(&B->copied, tun.sink_debug ? hipEventDefault : hipEventDisableTiming) == hipSuccess
                && hipMemcpyAsync((void*)B->stage, d_packed, (size_t)(hdr_bytes + pay_used), hipMemcpyDeviceToHost, c->copy_stream) == hipSuccess
                && (h_ncb == 0 || hipMemcpyAsync((void*)(B->stage + B->cb_off), d_cb, (size_t)h_ncb, hipMemcpyDeviceToHost, c->copy_stream) == hipSuccess)
                && (h_nexc == 0 || hipMemcpyAsync((void*)(B->stage + B->exc_off), d_exc, (size_t)h_nexc * 16, hipMemcpyDeviceToHost, c->copy_stream) == hipSuccess)
                && hipEventRecord(B->copied, c->copy_stream) == hipSuccess;
     if (!queued) { g_sink_why = "copy could not be queued"; (void)hipGetLastError(); (void)hipStreamSynchronize(c->copy_stream); if (B->copied) (void)hipEventDestroy(B->copied); delete B; c->dfree(d_packed); return nullptr; }
     B->t_queued = std::chrono::steady_clock::now(); B->pack_ms = std::chrono::duration<double, std::milli>(B->t_queued - t_pack0).count();
-    if (g_sink_debug) { std::lock_guard<std::mutex> lk(U->mu); if (U->all.empty()) fprintf(stderr, "[gkc sink] first batch queued %.1f ms after Stage B began\n", std::chrono::duration<double, std::milli>(B->t_queued - c->t_stage_b0).count()); }
+    if (tun.sink_debug) { std::lock_guard<std::mutex> lk(U->mu); if (U->all.empty()) fprintf(stderr, "[gkc sink] first batch queued %.1f ms after Stage B began\n", std::chrono::duration<double, std::milli>(B->t_queued - c->t_stage_b0).count()); }
     { std::lock_guard<std::mutex> lk(U->mu); U->all.push_back(B); U->queue.push_back(B); }
     U->cv.notify_all();
     return B;

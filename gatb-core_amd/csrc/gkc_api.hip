@@ -124,6 +124,7 @@ static void clear_segments(gkc_ctx* c)
 
 // Stage B of a detached pass (gkc_finish_pass_async) is in flight or not yet joined
 static bool bg_active(const gkc_ctx* c) { return c->stage_b_thread.joinable(); }
+bool gkc_stage_b_in_flight(const gkc_ctx* c) { return c->stage_b_running || bg_active(c); }
 // ... and the caller may go on with the NEXT pass meanwhile: one GPU (the exchange works on the context's own segment list), no host sink (it holds one pass)
 static bool bg_overlap_ok(const gkc_ctx* c) { return c->b_detached && c->comm_world == 1 && c->sink == nullptr; }
 // the detached pass is through: its records are no longer needed (another pass has been begun), or the lists go back to the context
@@ -236,7 +237,7 @@ int gkc_configure(gkc_ctx* c, uint32_t k, uint32_t m, uint32_t nb_partitions, ui
     const uint32_t def = k <= 31 ? 28 : 60;                      // min((8*sizeof(Type)-8)/2, 255), Sequence2SuperKmer.hpp:147
     if (c->maxs == 0 || c->maxs > def) c->maxs = def;
     c->datasets.assign((size_t)nb_partitions * nb_passes, Dataset());
-    c->pass_stats.assign(nb_passes, gkc_stats{}); c->pass_released.assign(nb_passes, 0); c->pass = 0; c->timing.clear(); c->in_pass = false;
+    c->pass_stats.assign(nb_passes, gkc_stats{}); c->pass_released.assign(nb_passes, 0); c->pass_epoch.assign(nb_passes, 0); c->pass = 0; c->timing.clear(); c->in_pass = false;
 
     GKC_TRY(c->ensure(c->d_repart, nm * 2));
     GKC_HIP(c, hipMemcpy(c->d_repart.p, repart, nm * 2, hipMemcpyHostToDevice));
@@ -340,6 +341,7 @@ int gkc_begin_pass(gkc_ctx* c, uint32_t pass)
         }
         for (uint32_t p = 0; p < c->nb_partitions; p++) c->datasets[(size_t)pass * c->nb_partitions + p] = Dataset();
         c->pass_stats[pass] = gkc_stats{}; c->pass_released[pass] = 0;
+        static std::atomic<uint64_t> epoch{0}; c->pass_epoch[pass] = ++epoch;
     }
     if (pass == 0) GKC_HIP(c, hipMemsetAsync(c->d_histo.p, 0, (size_t)c->nb_passes * ((size_t)c->histo_max + 1) * 8, c->stream));   // pass 0 starts a new run
     else GKC_HIP(c, hipMemsetAsync(c->histo_of(pass), 0, ((size_t)c->histo_max + 1) * 8, c->stream));                         // a pass that is run again starts from zero

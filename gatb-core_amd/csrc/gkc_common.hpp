@@ -333,6 +333,7 @@ struct gkc_ctx {
     std::mutex mu;                         // shared bookkeeping (timing, stats, outputs, error text) when Stage B runs two lanes
     hipStream_t lane_streams[3] = {nullptr, nullptr, nullptr};   // extra Stage-B lanes (created on first use)
     std::vector<uint8_t> pass_released;       // gkc_release_pass was called for the pass: whole-context consumers of the results refuse to run
+    std::vector<uint64_t> pass_epoch;         // process-wide serial number of the pass's latest gkc_begin_pass (0: never begun): gkc_banks_add tells results it has merged from a recount
     double d_hint = 0;                        // solid records per key of the last Stage-B pass (0 = none yet): sizes the next pass's batches
     std::map<std::string, Timing> timing;
     // scratch reused across calls
@@ -411,4 +412,5 @@ int gkc_comm_allreduce_or_words(gkc_comm* m, uint64_t* d_words, uint64_t n_words
 int gkc_comm_combine_seen_coll(gkc_comm* m, uint64_t* d_seen, uint64_t* d_coll, uint64_t n_words, hipStream_t st);
 void gkc_ctx_child_add(gkc_ctx* c);          // gkc_api.hip
 void gkc_ctx_child_release(gkc_ctx* c);      // destroys a closed context when its last child goes
+bool gkc_stage_b_in_flight(const gkc_ctx* c); // gkc_api.hip: Stage B of a gkc_finish_pass_async is running or not yet joined
 int gkc_alloc_histo(gkc_ctx* c);      // gkc_api.hip: fails when a pass of the context was released

@@ -29,7 +29,14 @@ SYMBOLS = [
     "gkc_comm_get_owners", "gkc_balanced_owner_ranges", "gkc_exchange", "gkc_comm_get_stats", "gkc_bloom_allreduce_or",
     "gkc_mphf_build_solid_dist", "gkc_mphf_abundance_map_dist", "gkc_exchange_plan",
     "gkc_sample_exact", "gkc_set_host_sink", "gkc_set_sink_mode", "gkc_finish_pass_async", "gkc_wait_partition", "gkc_finish_pass_wait",
+    "gkc_banks_create", "gkc_banks_destroy", "gkc_banks_add", "gkc_banks_evaluate", "gkc_banks_partition_info", "gkc_banks_partition_counts",
+    "gkc_banks_partition_vectors", "gkc_banks_partition_counts_device", "gkc_banks_histogram",
 ]
+
+# -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
+GKC_SOLIDITY_SUM, GKC_SOLIDITY_MIN, GKC_SOLIDITY_MAX, GKC_SOLIDITY_ONE, GKC_SOLIDITY_ALL, GKC_SOLIDITY_CUSTOM = range(6)
+SOLIDITY_KINDS = {"sum": GKC_SOLIDITY_SUM, "min": GKC_SOLIDITY_MIN, "max": GKC_SOLIDITY_MAX, "one": GKC_SOLIDITY_ONE, "all": GKC_SOLIDITY_ALL,
+                  "custom": GKC_SOLIDITY_CUSTOM}
 
 
 class GkcError(RuntimeError):
@@ -164,6 +171,15 @@ def lib():
         "gkc_wait_partition": (C.c_int, [vp, u32, u32, P(vp), P(u64)]),
         "gkc_finish_pass_wait": (C.c_int, [vp]),
         "gkc_exchange_plan": (C.c_int, [C.c_int, C.c_int, u32, vp, vp, u64, vp, P(PlanMsg), P(u32), P(PlanMsg), P(u32), P(u64)]),
+        "gkc_banks_create": (C.c_int, [vp, u32, P(vp)]),
+        "gkc_banks_destroy": (None, [vp]),
+        "gkc_banks_add": (C.c_int, [vp, vp, u32]),
+        "gkc_banks_evaluate": (C.c_int, [vp, C.c_int, vp, vp, vp, u32]),
+        "gkc_banks_partition_info": (C.c_int, [vp, u32, P(u64), P(u64)]),
+        "gkc_banks_partition_counts": (C.c_int, [vp, u32, vp, u64, P(u64)]),
+        "gkc_banks_partition_vectors": (C.c_int, [vp, u32, vp, u64, P(u64)]),
+        "gkc_banks_partition_counts_device": (C.c_int, [vp, u32, P(vp), P(vp), P(u64)]),
+        "gkc_banks_histogram": (C.c_int, [vp, vp, u32]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -395,6 +411,20 @@ class Counter:
         p = C.c_void_p(); n = C.c_uint64()
         self._chk(self.L.gkc_partition_counts_device(self.h, pass_, part, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def count_banks(self, banks, kind="sum", amin=1, amax=2147483647, solid_vec=None, histo_max=10000):
+        """counts every bank of ``banks`` — a list of (bases, offsets) — one after another, merges their counts on the device and evaluates the
+        solidity kind (what the reference does with an album of banks) -> the evaluated Banks object (bank i = banks[i])"""
+        b = Banks(self, len(banks))
+        try:
+            for i, (bases, offsets) in enumerate(banks):
+                self.count(bases, offsets)
+                b.add(i)
+            b.evaluate(kind, amin, amax, solid_vec, histo_max)
+        except Exception:
+            b.close()
+            raise
+        return b
 
     def all_counts(self):
         out = {}
@@ -765,6 +795,106 @@ class Bloom:
     def close(self):
         if getattr(self, "h", None):
             self.L.gkc_bloom_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Banks:
+    """gkc_banks: the counts of several banks merged on the device — per dataset the distinct k-mers of all banks with one abundance per bank — and the
+    reference's solidity kinds evaluated on them (include/gkc.h, multi-bank counting). Count bank i with ``counter`` (default solidity window), then
+    ``add(i)``; ``evaluate`` as often as needed; read with ``partition`` / ``vectors`` / ``histogram``."""
+    TILE = 1024          # k-mers one workgroup merges / scans at a time (csrc/gkc_banks.hip BK_TILE)
+    SCAN_BLOCK = 256     # tile sums the one-workgroup scan takes at a time (BK_SCAN_BLOCK)
+
+    def __init__(self, counter, nb_banks):
+        self.c = counter; self.L = counter.L; self.nb_banks = nb_banks
+        self.nb_datasets = counter.nb_partitions * counter.nb_passes
+        self.rec_bytes = counter.rec_bytes
+        self._ctx = C.c_void_p(counter.h.value)       # error messages live in the context the object was created from (alive as long as the object is)
+        h = C.c_void_p()
+        counter._chk(self.L.gkc_banks_create(counter.h, nb_banks, C.byref(h)))
+        self.h = h; self.histo_max = None
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise GkcError("gkc error %d: %s" % (rc, (self.L.gkc_last_error(self._ctx) or b"").decode()))
+
+    def add(self, bank, counter=None):
+        """every finished dataset of ``counter`` (default: the one the object was created from) becomes the column of ``bank``"""
+        self._chk(self.L.gkc_banks_add(self.h, (counter or self.c).h, bank))
+
+    def _per_bank(self, v, dtype):
+        a = np.asarray(v, dtype=dtype)
+        a = np.full(self.nb_banks, a, dtype=dtype) if a.ndim == 0 else np.ascontiguousarray(a)
+        if a.shape != (self.nb_banks,):
+            raise GkcError("one value per bank expected")
+        return a
+
+    def evaluate(self, kind="sum", amin=1, amax=2147483647, solid_vec=None, histo_max=10000):
+        """kind: "sum" | "min" | "max" | "one" | "all" | "custom" (or GKC_SOLIDITY_*); amin / amax: one value for every bank or one per bank"""
+        k = SOLIDITY_KINDS[kind] if isinstance(kind, str) else int(kind)
+        lo = self._per_bank(amin, np.int32); hi = self._per_bank(amax, np.int32)
+        sv = None if solid_vec is None else self._per_bank(solid_vec, np.uint8)
+        self._chk(self.L.gkc_banks_evaluate(self.h, k, _p(lo), _p(hi), _p(sv), histo_max))
+        self.histo_max = histo_max
+
+    def partition_info(self, dataset):
+        """-> (solid, distinct) k-mers of the dataset"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.gkc_banks_partition_info(self.h, dataset, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def partition_records(self, dataset):
+        """raw Count{value, sum} records of the dataset's solid k-mers (uint8 view)"""
+        ns, _ = self.partition_info(dataset)
+        out = np.zeros(max(1, ns * self.rec_bytes), np.uint8); n = C.c_uint64()
+        self._chk(self.L.gkc_banks_partition_counts(self.h, dataset, _p(out), ns, C.byref(n)))
+        return out[: ns * self.rec_bytes]
+
+    def partition(self, dataset):
+        """-> (lo uint64[], hi uint64[], abundance int32[]): the structured arrays of Counter.partition, abundance = sum over the banks"""
+        raw = self.partition_records(dataset)
+        w = self.rec_bytes // 8
+        r = raw.view(np.uint64).reshape(-1, w)
+        hi = np.zeros(len(r), np.uint64) if w == 2 else r[:, 1].copy()
+        return r[:, 0].copy(), hi, (r[:, w // 2] & np.uint64(0xFFFFFFFF)).astype(np.int32)
+
+    def vectors(self, dataset):
+        """-> int32[n_solid][nb_banks]: the abundance of every solid k-mer of the dataset in every bank, rows in the order of ``partition``"""
+        ns, _ = self.partition_info(dataset)
+        out = np.zeros((max(1, ns), self.nb_banks), np.int32); n = C.c_uint64()
+        self._chk(self.L.gkc_banks_partition_vectors(self.h, dataset, _p(out), ns, C.byref(n)))
+        return out[:ns]
+
+    def partition_device(self, dataset):
+        """-> (device pointer of the records, device pointer of the count vectors, n_solid)"""
+        p = C.c_void_p(); v = C.c_void_p(); n = C.c_uint64()
+        self._chk(self.L.gkc_banks_partition_counts_device(self.h, dataset, C.byref(p), C.byref(v), C.byref(n)))
+        return p.value, v.value, n.value
+
+    def histogram(self):
+        """histogram[min(sum, histo_max)] over all distinct k-mers of the last evaluation"""
+        hm = self.histo_max if self.histo_max is not None else 10000
+        h = np.zeros(hm + 1, np.uint64)
+        self._chk(self.L.gkc_banks_histogram(self.h, _p(h), hm + 1))
+        return h
+
+    def all_counts(self):
+        """{k-mer: tuple of its abundance in every bank} over the solid k-mers of all datasets"""
+        out = {}
+        for d in range(self.nb_datasets):
+            lo, hi, _ = self.partition(d)
+            for a, b, v in zip(lo.tolist(), hi.tolist(), self.vectors(d).tolist()):
+                out[(b << 64) | a] = tuple(v)
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gkc_banks_destroy(self.h); self.h = None
 
     def __del__(self):
         try:

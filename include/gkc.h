@@ -370,6 +370,48 @@ int      gkc_mphf_save(gkc_mphf* m, uint8_t* out, uint64_t cap);
  * for every solid k-mer of the context; *nb_above_precision = abundances beyond the table (MPHFAlgorithm.cpp:254-258) */
 int      gkc_mphf_abundance_map(gkc_mphf* m, gkc_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* nb_above_precision);
 
+/* ---- multi-bank counting: one abundance per bank and k-mer, solidity kinds ------------------------------------------------------
+ * Given an album of N banks the reference hands every count processor a CountVector with one abundance per bank, decides solidity with
+ * -solidity-kind sum|min|max|one|all|custom (kmer/impl/CountProcessorSolidity.hpp:176-304), dumps Count{kmer, sum}
+ * (CountProcessorDump.hpp:148-152) and histograms the sum (CountProcessorHistogram.hpp:173-184); known answers: test/unit/src/kmer/TestDSK.cpp:482-612.
+ * Here the banks are counted one after another by an ordinary context (window [1, INT32_MAX]: every distinct k-mer of the bank comes out) and a
+ * gkc_banks object merges their sorted Count[] arrays on the device: per dataset (part + pass * nb_partitions) the ascending distinct k-mers of all
+ * banks and nb_banks planes of int32 counts (0 where a bank does not have the k-mer). The object is built from a configured context, remembers its
+ * model (k, m, partitions, passes, minimizer order, repartition table) and keeps the context's allocator alive: it may outlive gkc_destroy of the
+ * context. Messages of every gkc_banks_* failure are read with gkc_last_error(the context the object was created from).
+ *   gkc_banks_add      : every finished dataset of `ctx` that the object has not merged yet becomes bank `bank`'s column (a multi-pass count may add
+ *                        after every pass or once after all of them: a pass's results are told apart from a recount by gkc_begin_pass). On return the
+ *                        context's results are no longer needed — gkc_begin_pass(ctx, 0) may start the next bank; the merged state owns its copies.
+ *                        Banks may be added in any order; a bank never added is a column of zeros. GKC_ERR_ARG when: the context's model differs from
+ *                        the object's; its solidity window is not the default [1, INT32_MAX] (per-bank counts must be complete); bank >= nb_banks; a
+ *                        (bank, dataset) pair is added twice (the same results again, or a recount into a bank that holds the dataset); a pass is open
+ *                        or was released (gkc_release_pass). Allowed after gkc_banks_evaluate: the evaluation is gone then.
+ *   gkc_banks_evaluate : one pass over the merged state: sum, min and max of every k-mer's counts, solid or not by `kind` with the closed ranges
+ *                        [amin[i], amax[i]] of bank i — sum / min / max look at range 0 only (_thresholds[0]); one: some bank's count in its range; all:
+ *                        every bank's; custom: bank i's count is in its range exactly when solid_vec[i] != 0 (CountProcessorSolidity.hpp:291-300) — and
+ *                        histogram[min(sum, histo_max)]++ over ALL distinct k-mers. May be repeated with other kinds and ranges without merging again.
+ *   reading (GKC_ERR_ARG before an evaluation): the solid k-mers of a dataset as Count{value, sum} records in the layout of gkc_partition_counts
+ *                        (16 / 32 bytes, ascending, pad bytes zero) and their count vectors int32[n_solid][nb_banks], on the host or where they lie.
+ * Counts and sums are int32 like CountNumber; a sum beyond INT32_MAX is outside the contract (it wraps). */
+#define GKC_SOLIDITY_SUM    0
+#define GKC_SOLIDITY_MIN    1
+#define GKC_SOLIDITY_MAX    2
+#define GKC_SOLIDITY_ONE    3
+#define GKC_SOLIDITY_ALL    4
+#define GKC_SOLIDITY_CUSTOM 5
+typedef struct gkc_banks gkc_banks;
+int  gkc_banks_create(gkc_ctx* ctx, uint32_t nb_banks /* 1..64 */, gkc_banks** out);
+void gkc_banks_destroy(gkc_banks* b);
+int  gkc_banks_add(gkc_banks* b, gkc_ctx* ctx, uint32_t bank);
+int  gkc_banks_evaluate(gkc_banks* b, int kind, const int32_t* amin /* [nb_banks] */, const int32_t* amax /* [nb_banks] */,
+                        const uint8_t* solid_vec /* [nb_banks], GKC_SOLIDITY_CUSTOM only, else NULL */, uint32_t histo_max);
+int  gkc_banks_partition_info(gkc_banks* b, uint32_t dataset, uint64_t* n_solid, uint64_t* n_distinct);
+int  gkc_banks_partition_counts(gkc_banks* b, uint32_t dataset, void* out_counts, uint64_t cap_records, uint64_t* n_solid);
+int  gkc_banks_partition_vectors(gkc_banks* b, uint32_t dataset, int32_t* out /* [n_solid][nb_banks] */, uint64_t cap_records, uint64_t* n_solid);
+/* device pointers into the evaluation's buffers: valid until the next gkc_banks_evaluate / gkc_banks_add / gkc_banks_destroy */
+int  gkc_banks_partition_counts_device(gkc_banks* b, uint32_t dataset, const void** d_counts, const int32_t** d_vectors, uint64_t* n_solid);
+int  gkc_banks_histogram(gkc_banks* b, uint64_t* out, uint32_t n_bins /* >= histo_max + 1 */);
+
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the
  * per-sequence copy into the flat buffer that gkc_push_reads takes. Same result as the reference reader for well-formed text:

@@ -317,6 +317,9 @@ struct gkc_banks {
     bool evaluated = false; uint32_t histo_max = 0;
     DevBuf out_counts, out_vectors, d_histo;
     std::vector<uint64_t> solid_off;                     // [n_ds + 1]: the datasets inside out_counts / out_vectors
+    // abundance queries (gkc_query_banks_reads_device): the routing tables of the model the object remembers — its own copies, the context may be configured again —
+    // and the sampled index over `keys`, built by the first query and dropped by gkc_banks_add
+    QueryModel qmodel{}; DevBuf q_repart, q_mkey_lut, q_key2val; QueryIndex qidx;
     uint64_t n_total() const { return off.empty() ? 0 : off.back(); }
     size_t key_bytes() const { return key_words == 1 ? 8 : 16; }
 };
@@ -415,6 +418,23 @@ int gkc_banks_create(gkc_ctx* c, uint32_t nb_banks, gkc_banks** out)
     b->n_ds = c->nb_partitions * c->nb_passes; b->model_hash = c->model_hash;
     b->planes.resize(nb_banks); b->off.assign((size_t)b->n_ds + 1, 0); b->added.assign((size_t)nb_banks * b->n_ds, 0); b->merged_epoch.assign(c->nb_passes, 0);
     gkc_ctx_child_add(c);
+    {   // the device tables a query routes k-mers with
+        const size_t nm = (size_t)1 << (2 * c->m);
+        const bool freq = c->minimizer_type == GKC_MINIMIZER_FREQ;
+        int rc = c->ensure(b->q_repart, nm * 2);
+        if (rc == GKC_OK && freq) rc = c->ensure(b->q_mkey_lut, nm * 4);
+        if (rc == GKC_OK && freq) rc = c->ensure(b->q_key2val, nm * 4);
+        hipError_t e = hipSuccess;
+        if (rc == GKC_OK) e = hipMemcpyAsync(b->q_repart.p, c->d_repart.p, nm * 2, hipMemcpyDeviceToDevice, c->stream);
+        if (rc == GKC_OK && freq && e == hipSuccess) e = hipMemcpyAsync(b->q_mkey_lut.p, c->d_mkey_lut.p, nm * 4, hipMemcpyDeviceToDevice, c->stream);
+        if (rc == GKC_OK && freq && e == hipSuccess) e = hipMemcpyAsync(b->q_key2val.p, c->d_key2val.p, nm * 4, hipMemcpyDeviceToDevice, c->stream);
+        if (rc == GKC_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (rc == GKC_OK && e != hipSuccess) { c->set_error(GKC_ERR_HIP, "gkc_banks_create: copying the model's tables failed: %s", hipGetErrorString(e)); rc = GKC_ERR_HIP; }
+        if (rc != GKC_OK) { delete b; gkc_ctx_child_release(c); return rc; }
+        QueryModel& M = b->qmodel;
+        M.k = c->k; M.m = c->m; M.nb_partitions = c->nb_partitions; M.nb_passes = c->nb_passes; M.key_words = c->key_words; M.freq_mode = freq ? 1 : 0; M.default_key = c->default_key;
+        M.repart = (const uint16_t*)b->q_repart.p; M.mkey_lut = (const uint32_t*)b->q_mkey_lut.p; M.key2val = (const uint32_t*)b->q_key2val.p;
+    }
     *out = b;
     return GKC_OK;
 }
@@ -459,6 +479,7 @@ int gkc_banks_add(gkc_banks* b, gkc_ctx* src, uint32_t bank)
     }
     ds[b->n_ds].a_off = b->off[b->n_ds]; ds[b->n_ds].b_first = n_b;
     if (src != c) (void)hipStreamSynchronize(src->stream);
+    b->qidx.drop();                                                // the merge replaces the key array the index samples
     if (n_b) {
         ScopedTimer tm(c, "banks_add");
         GKC_TRY(b->key_words == 1 ? bk_merge<1>(b, bank, ds, n_b) : bk_merge<2>(b, bank, ds, n_b));
@@ -563,6 +584,22 @@ int gkc_banks_partition_counts_device(gkc_banks* b, uint32_t dataset, const void
     if (d_vectors) *d_vectors = (const int32_t*)b->out_vectors.p + (size_t)first * b->nb_banks;
     if (n_solid) *n_solid = b->solid_off[dataset + 1] - first;
     return GKC_OK;
+}
+// the k-mers of reads against the merged state: the search of gkc_query_reads_device over the bare key array (gkc_query.hip), then the planes
+int gkc_query_banks_reads_device(gkc_banks* b, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, int32_t* d_sum, int32_t* d_vectors)
+{
+    gkc_tun_refresh();
+    if (!b) return GKC_ERR_ARG;
+    gkc_ctx* c = b->ctx;
+    GKC_HIP(c, hipSetDevice(c->device));
+    if (!b->qidx.valid || b->qidx.stride != gkc_tun().query_index_stride) {
+        std::vector<QHostDs> ds(b->n_ds);
+        for (uint32_t d = 0; d < b->n_ds; d++) ds[d] = QHostDs{(const uint8_t*)b->keys.p + (size_t)b->off[d] * b->key_bytes(), b->off[d + 1] - b->off[d], b->off[d]};
+        GKC_TRY(gkc_query_index_build(c, b->qidx, ds, b->key_words, true));
+    }
+    const int32_t* planes[BK_MAX_BANKS];
+    for (uint32_t p = 0; p < b->nb_banks; p++) planes[p] = (const int32_t*)b->planes[p].p;
+    return gkc_query_reads_run(c, b->qmodel, b->qidx, planes, b->nb_banks, d_bases, d_offsets, n_reads, n_bases, d_sum, d_vectors, "gkc_query_banks_reads_device");
 }
 int gkc_banks_histogram(gkc_banks* b, uint64_t* out, uint32_t n_bins)
 {

@@ -62,6 +62,8 @@ struct GkcTun {
     bool sink_packed, sink_packed2, sink_width6, sink_debug; int sink_adaptive; uint64_t sink_dense; int unpack_threads;
     // Bloom / MPHF
     bool bloom_atomic, bloom_gather, mphf_regions, mphf_ordered; uint64_t bloom_query_regions_min, mphf_regions_min;
+    // abundance queries
+    uint64_t query_index_stride;
     // allocator, communicators, diagnostics
     int vmm; uint32_t vmm_chunk_mb, vmm_min_mb; bool vmm_with_rccl, pool_debug, pool_trace, verbose; double filebox_timeout; char fault[32];       // (plain data: concurrent refreshes of equal values are harmless)
     static const char* raw(const char* name) { return getenv(name); }
@@ -81,6 +83,7 @@ struct GkcTun {
         sink_dense = (uint64_t)num("GKC_SINK_DENSE", 0); unpack_threads = (int)num("GKC_UNPACK_THREADS", 0);
         bloom_atomic = on("GKC_BLOOM_ATOMIC"); bloom_gather = on("GKC_BLOOM_GATHER"); mphf_regions = not0("GKC_MPHF_REGIONS"); mphf_ordered = on("GKC_MPHF_ORDERED");
         bloom_query_regions_min = (uint64_t)num("GKC_BLOOM_QUERY_REGIONS_MIN", 2000000); mphf_regions_min = (uint64_t)num("GKC_MPHF_REGIONS_MIN", 1ll << 21);
+        query_index_stride = (uint64_t)std::min<long long>(1ll << 40, std::max<long long>(1, num("GKC_QUERY_INDEX_STRIDE", 256)));      /* records per sample of the query index */
         vmm = (int)num("GKC_VMM", 1); vmm_chunk_mb = (uint32_t)std::max<long long>(2, num("GKC_VMM_CHUNK_MB", 1024)); vmm_min_mb = (uint32_t)std::max<long long>(1, num("GKC_VMM_MIN_MB", 64));
         vmm_with_rccl = num("GKC_VMM_WITH_RCCL", 0) == 1; pool_debug = on("GKC_POOL_DEBUG"); pool_trace = on("GKC_POOL_TRACE"); verbose = on("GKC_VERBOSE");
         filebox_timeout = raw("GKC_FILEBOX_TIMEOUT") ? atof(raw("GKC_FILEBOX_TIMEOUT")) : 600.0; memset(fault, 0, sizeof fault); if (raw("GKC_FAULT")) strncpy(fault, raw("GKC_FAULT"), sizeof fault - 1);
@@ -271,6 +274,21 @@ struct Dataset {                          // result of (pass, part)
 
 struct Timing { double ms = 0; uint64_t launches = 0; };
 
+// Abundance queries (gkc_query.hip): the sampled index over one result state — the finished datasets of a context, or the merged keys of a gkc_banks — and the
+// device table of its datasets. Built by the first query, dropped (valid = false) when the state it describes is gone.
+struct QueryIndex {
+    DevBuf table, samples;                // QDs[n_ds] and the key of every stride-th record of every dataset, dataset after dataset
+    uint64_t stride = 0; bool valid = false;
+    std::vector<uint64_t> epoch;          // gkc_ctx::pass_epoch when it was built ...
+    std::vector<std::pair<const void*, uint64_t>> sig;   // ... and where the datasets lay (gkc_gather_results moves them without a new pass)
+    void drop() { valid = false; table.release(); samples.release(); }
+};
+struct QHostDs { const void* recs; uint64_t n, base; };      // one dataset: its ascending records / keys, how many, and its place in the state's flat order (banks: the planes)
+struct QueryModel {                       // what routes a k-mer to its dataset
+    uint32_t k, m, nb_partitions, nb_passes, key_words; int freq_mode; uint32_t default_key;
+    const uint32_t* mkey_lut; const uint32_t* key2val; const uint16_t* repart;
+};
+
 struct gkc_unpacker;                      // gkc_sink.hip: staging buffer + host threads that expand packed result batches into the sink
 struct gkc_ctx {
     int device = 0;
@@ -336,6 +354,7 @@ struct gkc_ctx {
     std::vector<uint64_t> pass_epoch;         // process-wide serial number of the pass's latest gkc_begin_pass (0: never begun): gkc_banks_add tells results it has merged from a recount
     double d_hint = 0;                        // solid records per key of the last Stage-B pass (0 = none yet): sizes the next pass's batches
     std::map<std::string, Timing> timing;
+    QueryIndex qidx;                          // gkc_query_*: index over the finished datasets
     // scratch reused across calls
     DevBuf d_scan_counters;    // u64[2P + 8]
     DevBuf d_rsbits;           // read-start bitmask
@@ -392,6 +411,12 @@ int gkc_scan_count_mmers(gkc_ctx* c, uint32_t m, const char* d_bases, const uint
 int gkc_export_superkmers(gkc_ctx* c, uint32_t part, uint8_t* out, uint64_t cap, uint64_t* nb, uint64_t* nsk, uint64_t* nk);
 
 int gkc_require_resident(gkc_ctx* c, const char* who);
+int gkc_launch_mark_read_starts(gkc_ctx* c, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_bits, uint32_t* d_bad);      // gkc_scan.hip
+// gkc_query.hip: (re)builds ix over `ds` at the current GKC_QUERY_INDEX_STRIDE (bare: 8 / 16-byte keys, else Count records); the reads kernel against it — planes != nullptr: the
+// merged state of a gkc_banks, d_out = sum over the nb_banks planes and d_vectors (may be NULL) the rows
+int gkc_query_index_build(gkc_ctx* c, QueryIndex& ix, const std::vector<QHostDs>& ds, uint32_t key_words, bool bare);
+int gkc_query_reads_run(gkc_ctx* c, const QueryModel& M, const QueryIndex& ix, const int32_t* const* planes, uint32_t nb_banks, const char* d_bases, const uint64_t* d_offsets,
+                        uint64_t n_reads, uint64_t n_bases, int32_t* d_out, int32_t* d_vectors, const char* who);
 // packed result batches (gkc_sink.hip). tun: the tunables the call works with — a Stage-B lane hands in its pass's snapshot, everyone else gkc_tun()
 bool  gkc_sink_packed(gkc_ctx* c, const GkcTun& tun);
 bool  gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records, const GkcTun& tun);   // several ranks on one host: landed, unexpanded records beyond 1.5 batches -> this batch travels raw

@@ -83,6 +83,48 @@ template <> struct KeyT<2> {
 // 16 B (RW=2) holds 60 nt (k<=31, nbK<=28 -> k+nbK-1 <= 58); 32 B (RW=4) holds 124 nt (k<=63, nbK<=60 -> <=122).
 template <int RW> struct RecT { uint64_t w[RW]; };
 
+// ---- ASCII -> 2-bit planes, 16 bases at a time (Stage A tiles, the query tiles) ----
+// 16 ASCII bases (4 dwords) -> little-endian 2-bit word + invalid mask (A1), SWAR
+__device__ __forceinline__ void encode16(const uint32_t (&dw)[4], uint32_t& le, uint32_t& bad)
+{
+    le = 0; bad = 0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t wv = dw[q];
+        uint32_t c4 = (wv >> 1) & 0x03030303u;
+        c4 = (c4 | (c4 >> 6)) & 0x000F000Fu;
+        c4 = (c4 | (c4 >> 12)) & 0xFFu;                                     // c0 | c1<<2 | c2<<4 | c3<<6
+        le |= c4 << (8 * q);
+        const uint32_t u = wv & 0xDFDFDFDFu;
+        auto nz = [](uint32_t v) { return (((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u; };   // 0x80 where the byte is non-zero
+        uint32_t b4 = nz(u ^ 0x41414141u) & nz(u ^ 0x43434343u) & nz(u ^ 0x47474747u) & nz(u ^ 0x54545454u);
+        b4 >>= 7;
+        b4 = (b4 | (b4 >> 7) | (b4 >> 14) | (b4 >> 21)) & 0xFu;
+        bad |= b4 << (4 * q);
+    }
+}
+__device__ __forceinline__ uint32_t rev2bit(uint32_t x)                         // reverse the 16 two-bit groups
+{
+    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+    return __builtin_bswap32(x);
+}
+__device__ __forceinline__ void load16(const uint8_t* bases, uint64_t g0, uint64_t n_bases, uint32_t (&dw)[4])
+{
+    if (g0 + 16 <= n_bases) {
+        const uint4 v = *reinterpret_cast<const uint4*>(bases + g0);
+        dw[0] = v.x; dw[1] = v.y; dw[2] = v.z; dw[3] = v.w;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int b = 0; b < 4; b++) { const uint64_t g = g0 + 4 * q + b; const uint32_t c = (g < n_bases) ? bases[g] : 0u; x |= c << (8 * b); }
+            dw[q] = x;
+        }
+    }
+}
+
 // wave64 helpers
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 

@@ -76,6 +76,16 @@ __global__ void k_mark_read_starts(const uint64_t* __restrict__ offsets, uint64_
     }
 }
 
+// the mask and the offsets check for callers outside Stage A (gkc_query.hip): d_bits zeroed by the caller, *d_bad set when the offsets are no CSR table of n_bases bases
+int gkc_launch_mark_read_starts(gkc_ctx* c, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_bits, uint32_t* d_bad)
+{
+    const uint64_t n_entries = n_reads + 1;
+    hipLaunchKernelGGL(k_mark_read_starts, dim3((unsigned)std::min<uint64_t>((n_entries + 255) / 256, 4096)), dim3(256), 0, c->stream, d_offsets, n_entries, n_bases, d_bits, d_bad,
+                       (unsigned long long*)nullptr);
+    GKC_HIP(c, hipGetLastError());
+    return GKC_OK;
+}
+
 // LDS index of per-position arrays: thread t owns positions 16t..16t+15; one pad word per 16 entries makes the lane
 // stride 17 dwords, so the 32 lanes of an LDS access group hit 32 different banks (stride 16 would be a 16-way conflict)
 #define MKI(p) ((p) + ((p) >> 4))
@@ -110,47 +120,6 @@ __device__ __forceinline__ void store_record(const uint32_t* s_be, int start, ui
     uint64_t* dst = arena + slot * RW;
 #pragma unroll
     for (int i = 0; i < RW; i += 2) store16(dst + i, R[i], R[i + 1]);
-}
-
-// 16 ASCII bases (4 dwords) -> little-endian 2-bit word + invalid mask (A1), SWAR
-__device__ __forceinline__ void encode16(const uint32_t (&dw)[4], uint32_t& le, uint32_t& bad)
-{
-    le = 0; bad = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t wv = dw[q];
-        uint32_t c4 = (wv >> 1) & 0x03030303u;
-        c4 = (c4 | (c4 >> 6)) & 0x000F000Fu;
-        c4 = (c4 | (c4 >> 12)) & 0xFFu;                                     // c0 | c1<<2 | c2<<4 | c3<<6
-        le |= c4 << (8 * q);
-        const uint32_t u = wv & 0xDFDFDFDFu;
-        auto nz = [](uint32_t v) { return (((v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | v) & 0x80808080u; };   // 0x80 where the byte is non-zero
-        uint32_t b4 = nz(u ^ 0x41414141u) & nz(u ^ 0x43434343u) & nz(u ^ 0x47474747u) & nz(u ^ 0x54545454u);
-        b4 >>= 7;
-        b4 = (b4 | (b4 >> 7) | (b4 >> 14) | (b4 >> 21)) & 0xFu;
-        bad |= b4 << (4 * q);
-    }
-}
-__device__ __forceinline__ uint32_t rev2bit(uint32_t x)                         // reverse the 16 two-bit groups
-{
-    x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
-    x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
-    return __builtin_bswap32(x);
-}
-__device__ __forceinline__ void load16(const uint8_t* bases, uint64_t g0, uint64_t n_bases, uint32_t (&dw)[4])
-{
-    if (g0 + 16 <= n_bases) {
-        const uint4 v = *reinterpret_cast<const uint4*>(bases + g0);
-        dw[0] = v.x; dw[1] = v.y; dw[2] = v.z; dw[3] = v.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; b++) { const uint64_t g = g0 + 4 * q + b; const uint32_t c = (g < n_bases) ? bases[g] : 0u; x |= c << (8 * b); }
-            dw[q] = x;
-        }
-    }
 }
 
 // LDSPART: persistent workgroups with a static tile assignment (tile = blockIdx.x, += gridDim.x, identical in the count

@@ -31,6 +31,7 @@ SYMBOLS = [
     "gkc_sample_exact", "gkc_set_host_sink", "gkc_set_sink_mode", "gkc_finish_pass_async", "gkc_wait_partition", "gkc_finish_pass_wait",
     "gkc_banks_create", "gkc_banks_destroy", "gkc_banks_add", "gkc_banks_evaluate", "gkc_banks_partition_info", "gkc_banks_partition_counts",
     "gkc_banks_partition_vectors", "gkc_banks_partition_counts_device", "gkc_banks_histogram",
+    "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -62,6 +63,10 @@ class PlanMsg(C.Structure):
 class CommStats(C.Structure):
     _fields_ = [("n_exchanges", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("ms_transfer", C.c_double),
                 ("ms_host", C.c_double), ("reserved", C.c_uint64 * 4)]
+
+
+# gkc_read_abundance (include/gkc.h) as a numpy record
+READ_ABUNDANCE = np.dtype([("n_valid", np.uint32), ("n_found", np.uint32), ("min", np.int32), ("max", np.int32), ("sum", np.uint64)])
 
 
 class Stats(C.Structure):
@@ -180,6 +185,12 @@ def lib():
         "gkc_banks_partition_vectors": (C.c_int, [vp, u32, vp, u64, P(u64)]),
         "gkc_banks_partition_counts_device": (C.c_int, [vp, u32, P(vp), P(vp), P(u64)]),
         "gkc_banks_histogram": (C.c_int, [vp, vp, u32]),
+        "gkc_query_reads_device": (C.c_int, [vp, vp, vp, u64, u64, vp]),
+        "gkc_query_reads": (C.c_int, [vp, vp, vp, u64, vp]),
+        "gkc_query_kmers_device": (C.c_int, [vp, vp, u64, u32, vp]),
+        "gkc_query_kmers": (C.c_int, [vp, vp, u64, u32, vp]),
+        "gkc_query_read_summary_device": (C.c_int, [vp, vp, vp, u64, vp]),
+        "gkc_query_banks_reads_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -549,6 +560,72 @@ class Counter:
         self._chk(self.L.gkc_result_checksum(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    # ---- abundance queries against the finished datasets (include/gkc.h, "abundance queries")
+    def query_reads(self, bases, offsets):
+        """-> int32[n_bases]: per position of the flat buffer the abundance of the k-mer starting there (> 0), 0 = valid k-mer not in the results, -1 = no k-mer"""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offsets) < 1 or int(offsets[-1]) > len(bases):
+            raise GkcError("the offsets end beyond the bases")
+        out = np.zeros(int(offsets[-1]), np.int32)
+        self._chk(self.L.gkc_query_reads(self.h, _p(bases), _p(offsets), len(offsets) - 1, _p(out)))
+        return out
+
+    def query_reads_device(self, d_bases, d_offsets, n_reads, n_bases, d_out):
+        """the same where the reads lie: device pointers, d_bases and d_out 16-byte aligned, d_out int32[n_bases]"""
+        self._chk(self.L.gkc_query_reads_device(self.h, d_bases, d_offsets, n_reads, n_bases, d_out))
+
+    def _query_keys(self, keys):
+        """keys: ints, a uint64 array (k <= 31), a uint64[n][2] array of (low, high) words (k <= 63), or raw Count records (the uint8 view of
+        partition_records) -> (array, n, stride in bytes)"""
+        kb = 8 if self.k <= 31 else 16
+        if isinstance(keys, np.ndarray) and keys.dtype == np.uint8:
+            a = np.ascontiguousarray(keys)
+            if a.nbytes % self.rec_bytes:
+                raise GkcError("a uint8 key array holds whole Count records of %d bytes" % self.rec_bytes)
+            return a, a.nbytes // self.rec_bytes, self.rec_bytes
+        if isinstance(keys, np.ndarray) and keys.dtype == np.uint64:
+            a = np.ascontiguousarray(keys)
+            if a.nbytes % kb:
+                raise GkcError("a uint64 key array holds %d words per key" % (kb // 8))
+            return a, a.nbytes // kb, kb
+        ks = [int(x) for x in keys]
+        if kb == 8:
+            a = np.array([x & M64 if x >> 64 == 0 else M64 for x in ks], dtype=np.uint64)      # (a value beyond 64 bits is no k-mer for k <= 31: all ones is refused too)
+            return a, len(ks), 8
+        a = np.zeros((len(ks), 2), np.uint64)
+        a[:, 0] = [x & M64 for x in ks]; a[:, 1] = [(x >> 64) & M64 for x in ks]
+        return a, len(ks), 16
+
+    def query_kmers(self, keys):
+        """-> int32[n]: the abundance of min(key, revcomp(key)) in the results, or 0 (keys: see _query_keys)"""
+        a, n, stride = self._query_keys(keys)
+        out = np.zeros(n, np.int32)
+        self._chk(self.L.gkc_query_kmers(self.h, _p(a) if n else None, n, stride, _p(out) if n else None))
+        return out
+
+    def query_kmers_device(self, d_keys, n, stride, d_out):
+        self._chk(self.L.gkc_query_kmers_device(self.h, d_keys, n, stride, d_out))
+
+    def query_read_summary_device(self, d_abund, d_offsets, n_reads, d_out):
+        """d_out: gkc_read_abundance[n_reads] (24 bytes each) on the device"""
+        self._chk(self.L.gkc_query_read_summary_device(self.h, d_abund, d_offsets, n_reads, d_out))
+
+    def query_read_summary(self, abund, offsets):
+        """per read of an abundance array made by query_reads with the same offsets -> records of READ_ABUNDANCE (n_valid, n_found, min, max, sum)"""
+        import torch
+        abund = np.ascontiguousarray(abund, dtype=np.int32); offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n = len(offsets) - 1
+        if n <= 0:
+            return np.zeros(0, READ_ABUNDANCE)
+        if int(offsets[-1]) > len(abund):
+            raise GkcError("the offsets end beyond the abundance array")
+        ta = torch.from_numpy(abund.view(np.uint8).copy()).cuda() if len(abund) else torch.zeros(16, dtype=torch.uint8, device="cuda")
+        to = torch.from_numpy(offsets.view(np.uint8).copy()).cuda()
+        tr = torch.zeros(n * READ_ABUNDANCE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self.query_read_summary_device(ta.data_ptr(), to.data_ptr(), n, tr.data_ptr())
+        return tr.cpu().numpy().view(READ_ABUNDANCE).copy()
+
 
 def balanced_owner_ranges(weights, world):
     """contiguous partition ranges per rank balanced by weight (pure host function of the library): first[world+1]"""
@@ -875,6 +952,26 @@ class Banks:
         p = C.c_void_p(); v = C.c_void_p(); n = C.c_uint64()
         self._chk(self.L.gkc_banks_partition_counts_device(self.h, dataset, C.byref(p), C.byref(v), C.byref(n)))
         return p.value, v.value, n.value
+
+    def query_reads_device(self, d_bases, d_offsets, n_reads, n_bases, d_sum, d_vectors=None):
+        self._chk(self.L.gkc_query_banks_reads_device(self.h, d_bases, d_offsets, n_reads, n_bases, d_sum, d_vectors))
+
+    def query_reads(self, bases, offsets, vectors=True):
+        """the k-mers of the reads against the merged state (no evaluation needed) -> (int32[n_bases] sum over the banks, > 0 / 0 / -1 like Counter.query_reads,
+        int32[n_bases][nb_banks] rows or None)"""
+        import torch
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        nb = len(bases)
+        tb = torch.zeros(nb + 64, dtype=torch.uint8, device="cuda")
+        if nb:
+            tb[:nb] = torch.from_numpy(bases.copy()).cuda()
+        to = torch.from_numpy(offsets.view(np.uint8).copy()).cuda()
+        ts = torch.zeros(nb + 16, dtype=torch.int32, device="cuda")
+        tv = torch.zeros(nb * self.nb_banks + 16, dtype=torch.int32, device="cuda") if vectors else None
+        torch.cuda.synchronize()
+        self.query_reads_device(tb.data_ptr(), to.data_ptr(), len(offsets) - 1, nb, ts.data_ptr(), tv.data_ptr() if vectors else None)
+        sums = ts.cpu().numpy()[:nb].copy()
+        return sums, (tv.cpu().numpy()[: nb * self.nb_banks].reshape(nb, self.nb_banks).copy() if vectors else None)
 
     def histogram(self):
         """histogram[min(sum, histo_max)] over all distinct k-mers of the last evaluation"""

@@ -187,7 +187,8 @@ typedef struct gkc_stats {
 int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
- * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b" */
+ * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
+ * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -411,6 +412,34 @@ int  gkc_banks_partition_vectors(gkc_banks* b, uint32_t dataset, int32_t* out /*
 /* device pointers into the evaluation's buffers: valid until the next gkc_banks_evaluate / gkc_banks_add / gkc_banks_destroy */
 int  gkc_banks_partition_counts_device(gkc_banks* b, uint32_t dataset, const void** d_counts, const int32_t** d_vectors, uint64_t* n_solid);
 int  gkc_banks_histogram(gkc_banks* b, uint64_t* out, uint32_t n_bins /* >= histo_max + 1 */);
+
+/* ---- abundance queries: the k-mers of reads, or bare k-mer values, looked up in the counted results on the device -----------------------------
+ * The reference answers "how often was this k-mer seen" through the MPHF + abundance map (discretised, keys of the set only) or by opening the result file; here the
+ * finished datasets are searched where they lie. A k-mer's dataset follows from its minimizer (repart[minimizer], minimizer % nb_passes), each dataset is an ascending
+ * Count[]; a sampled index (the key of every GKC_QUERY_INDEX_STRIDE-th record, default 256) is built by the first query, owned by the context and dropped when its
+ * results change: a query always answers from the results the context holds NOW (after a recount — gkc_begin_pass(0) ... gkc_finish_pass — the new counts).
+ * State (GKC_ERR_ARG otherwise, gkc_last_error names the reason): the context is configured, no pass is open, EVERY dataset of every pass is finished, no pass was
+ * released (gkc_release_pass), no gkc_finish_pass_async is in flight. Offsets are checked like gkc_push_reads_device checks them; bad offsets touch no memory outside
+ * the buffers. Queries across the ranks of a communicator are not provided: every rank answers from the datasets it holds, and on the root after gkc_gather_results
+ * the calls serve every partition like any other call.
+ * out[g], g = index of the k-mer's FIRST base in the flat buffer (n_bases entries, 4 bytes per base; device arrays 16-byte aligned like d_bases):
+ *   > 0  the Count abundance of the canonical k-mer (it is in the results, i.e. inside the solidity window of the count)
+ *     0  a valid k-mer that is not in the results
+ *    -1  no k-mer starts here: fewer than k bases left in the read, or the window holds a character outside ACGTacgt
+ * Timing names of gkc_get_timing: "query_index", "query_reads", "query_kmers". */
+int gkc_query_reads_device(gkc_ctx* ctx, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, int32_t* d_out);
+int gkc_query_reads(gkc_ctx* ctx, const char* bases, const uint64_t* offsets, uint64_t n_reads, int32_t* out);   /* host in, host out */
+/* keys: n items `stride` bytes apart, the k-mer value in the first 8 (k <= 31) / 16 (k <= 63) bytes, like gkc_bloom_insert (a Count array works as it is).
+ * The library takes min(key, revcomp(key)). out[i] = abundance or 0. A value >= 4^k: GKC_ERR_ARG. */
+int gkc_query_kmers_device(gkc_ctx* ctx, const void* d_keys, uint64_t n, uint32_t stride, int32_t* d_out);
+int gkc_query_kmers(gkc_ctx* ctx, const void* keys, uint64_t n, uint32_t stride, int32_t* out);
+/* per read, from an abundance array as written above and the offsets it was made with: over the read's valid k-mers (0 counts as a value) */
+typedef struct gkc_read_abundance { uint32_t n_valid, n_found; int32_t min, max; uint64_t sum; } gkc_read_abundance;   /* all 0 when n_valid == 0 */
+int gkc_query_read_summary_device(gkc_ctx* ctx, const int32_t* d_abund, const uint64_t* d_offsets, uint64_t n_reads, gkc_read_abundance* d_out);
+/* the same against a merged multi-bank state (needs no gkc_banks_evaluate, stays valid across evaluations; gkc_banks_add drops the object's index):
+ * d_sum[g] as above with the sum over banks; d_vectors (may be NULL): int32[n_bases][nb_banks], row of zeros where d_sum[g] <= 0.
+ * Errors are read with gkc_last_error(the context the object was created from). (Named gkc_query_*: the gkc_banks_* exports are a closed list, tests/test_banks_cpu.py.) */
+int gkc_query_banks_reads_device(gkc_banks* b, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, int32_t* d_sum, int32_t* d_vectors);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

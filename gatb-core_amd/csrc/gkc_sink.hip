@@ -6,12 +6,16 @@
 //     records whose abundance is NOT 1: 6 bytes of delta + 1 bit in the block's bitmap + a byte in the batch's abundance stream for those = 6.3 bytes (PK6)
 //     — and since round 6 the deltas of that format are bit-packed at the width of the largest delta of their sub-block of 128 records, one width byte per sub-block,
 //     8- and 16-byte keys alike (PKV below): 5.8 bytes per record at k = 31, 14.5 of 32 at k = 63 (10^8 reads), no key escapes
+//     — and with 8-byte keys a sub-block has TWO widths where that pays: a third of the gaps are the small ones between an error k-mer and its parent, they travel at a
+//     short width of their own behind a selector bitmap of 16 bytes (PKV with two widths below; GKC_SINK_TWO_WIDTHS=0 keeps one): 5.34 bytes per record at k = 31
 // and library threads on the host expand it into the exact in-memory layout of Kmer<span>::Count ({u64 value; i32 abundance; pad}, Abundance.hpp:68-129) at its
 // place in the caller's sink: what gkc_wait_partition hands out is byte for byte what the unpacked copy would have been (tests: the sink against
 // gkc_partition_counts). Rare values leave through an exception list (record index, value): a delta of 2^48-1 or more (the delta field then holds the escape
 // 0xFFFFFFFFFFFF), an abundance of 255 or more (escape 255). The reference's sink this stands in for is CountProcessorDump -> BagCache -> CollectionHDF5Patch
 // (CountProcessorDump.hpp:148-152): the consumer of whole Count[] blocks.
-//   device   k_pack_counts: one workgroup per block (blocks never straddle partitions, each has its own 16-byte-aligned 57344-byte slot), records -> 7-byte
+//   device   k_pack_counts6t (two widths), k_pack_counts6 / k_pack_pkv2 (one width): one workgroup per block, two passes over its records (widths, then the packing
+//            through LDS), ONE atomic reservation each in the batch's payload stream and abundance stream, the payload starts on 16 bytes and leaves LDS as 16-byte words
+//            k_pack_counts: one workgroup per block (blocks never straddle partitions, each has its own 16-byte-aligned 57344-byte slot), records -> 7-byte
 //            entries staged through LDS and written as 16-byte words; reads the batch's Count[] once, writes 0.44x of it
 //   link     ONE copy per Stage-B batch on the copy stream: [block bases | payload] then the exception entries, into a page-locked staging buffer of the library
 //   host     a pool of unpack threads: the first to reach a batch waits for its copy (HIP event) and sorts the exceptions, then all of them take blocks off an
@@ -48,6 +52,19 @@ constexpr uint64_t PK_DENSE = 300000;                                   // recor
 // the streams is whatever it came out as. W > 56 (a host extraction reads 8 bytes at any bit offset: 7 + W <= 63) is sent as W = 64.
 constexpr uint32_t PKV_CHUNK = 2048, PKV_SUB = 128, PKV_NSUB = PK_BLOCK / PKV_SUB;                              // records per pack iteration (256 threads x 8); per width; widths per block
 constexpr uint64_t PKV_BITMAP = PK_BLOCK / 8, PKV_BLOCK_MAX = (uint64_t)PK_BLOCK * 8 + PKV_BITMAP;              // worst case of a block's payload (W = 64)
+// PKV with TWO widths per sub-block (8-byte keys; the default, GKC_SINK_TWO_WIDTHS=0 keeps the one above): the gaps of a partition are NOT independent. At 30x with 1 %
+// substitutions 84 % of the distinct k-mers are one-nucleotide variants of a genomic k-mer, and a variant that keeps its minimizer and strand lands INSIDE its parent's
+// gap of 2^42: a third of all gaps are small, log-uniform over 1..35 bits, and one width per sub-block sends them all at the ~45 bits of the largest. Here a sub-block has
+// a long width wl (its largest delta, as above) and a short one ws: the EXACT minimum of 16 + ceil(n_short ws / 8) + ceil(n_long wl / 8) over ws < wl, from a histogram
+// of the sub-block's bit lengths. A sub-block that gains 16 bytes or more by it travels as
+//     [selector bitmap: 16 bytes, bit i = record i is long][its short deltas at ws bits, in record order, padded to a byte][its long deltas at wl bits, likewise]
+// every other one as its deltas at wl bits with ws = wl and NO bitmap (of a sub-block's records only: the last one of a partition is shorter than 16 wl bytes). Two
+// width bytes per sub-block in the header ([wl x 64][ws x 64] per block); the 16 sub-blocks of a pack iteration are padded to 16 bytes together, so a block's payload
+// [abundance bitmap][sub-blocks] still starts on 16 bytes and leaves LDS as 16-byte words — and since a split gains at least what that padding costs, a block is never
+// larger than under one width. ws <= 56 (a host extraction reads 8 bytes at any bit offset).
+constexpr uint32_t PKV_SEL = PKV_SUB / 8;                                                                         // bytes of a sub-block's selector bitmap
+constexpr uint64_t PKVT_CHUNK_MAX = (uint64_t)(PKV_CHUNK / PKV_SUB) * (PKV_SEL + PKV_SUB * 8);                    // (an upper bound: a split sub-block is smaller than 128 x 8 bytes)
+constexpr uint64_t PKVT_BLOCK_MAX = (uint64_t)PK_BLOCK * 8 + (uint64_t)PKV_NSUB * PKV_SEL + PKV_BITMAP;
 // PKV for 16-byte keys (reported as width 14; round 6): the same layout with 128-bit deltas — a sub-block's width W is 0..128 bits, a record's W bits are the low
 // min(W, 64) bits of its delta followed by the W - 64 high ones; bases are 16 bytes per block. k = 63, 5.6e5 records per partition: gaps of 2^107 on average, 13.7 bytes
 // per record where the fixed entries carry 15 or 16 (+ escapes).
@@ -220,6 +237,170 @@ __global__ __launch_bounds__(PK_THREADS) void k_pack_counts6(const uint64_t* __r
         __syncthreads();
     }
     if (t < PKV_BITMAP / 16) reinterpret_cast<uint4*>(dstp + s_off[PKV_NSUB])[t] = reinterpret_cast<const uint4*>(s_bits)[t];      // the bitmap: 1024 bytes = 64 x 16
+    uint8_t* cb = cb_stream + s_base;
+    for (uint32_t i = t; i < run; i += PK_THREADS) cb[i] = s_cb[i];
+}
+
+// PKV with two widths per sub-block (see PKVT_BLOCK_MAX above): wbits = [nblk][2 PKV_NSUB] (long widths, then short ones). A thread's 8 records go to bit positions
+// that depend on the selector bits before them, so the streams are OR-ed into zeroed LDS words (64-bit LDS atomics) instead of written byte by byte.
+__global__ __launch_bounds__(PK_THREADS) void k_pack_counts6t(const uint64_t* __restrict__ recs, PackPlan P, uint64_t* __restrict__ bases, uint32_t* __restrict__ cb_off,
+                                                              uint32_t* __restrict__ pay_off16, uint8_t* __restrict__ wbits /* [nblk][2 PKV_NSUB] */,
+                                                              uint8_t* __restrict__ payload, unsigned long long* __restrict__ pay_cursor /* bytes */,
+                                                              uint8_t* __restrict__ cb_stream, unsigned long long* __restrict__ cb_cursor,
+                                                              uint64_t* __restrict__ exc, unsigned long long* __restrict__ n_exc, uint32_t exc_cap)
+{
+    constexpr uint32_t NCH = PK_BLOCK / PKV_CHUNK, SPC = PKV_CHUNK / PKV_SUB;                // pack iterations per block, sub-blocks per iteration
+    constexpr uint32_t OUT_WORDS = (uint32_t)(PKVT_CHUNK_MAX / 8) + 2;
+    __shared__ __attribute__((aligned(16))) unsigned long long s_out[OUT_WORDS];              // one chunk's sub-blocks (+ the word a last delta may spill zeros into)
+    __shared__ uint64_t s_key[PKV_CHUNK + 1];                                                 // the chunk's keys, [0] = the key before the chunk
+    __shared__ __attribute__((aligned(16))) unsigned long long s_bits[PK_BLOCK / 64];
+    __shared__ __attribute__((aligned(16))) uint8_t s_cb[PK_BLOCK];
+    __shared__ unsigned long long s_wmax[2];                                                  // per round of pass 1 (2 sub-blocks): the largest delta,
+    __shared__ uint32_t s_hist[2][64];                                                        //   records per bit length (57..64 counted as 63: never a short width)
+    __shared__ uint32_t s_wl[PKV_NSUB], s_ws[PKV_NSUB], s_ns[PKV_NSUB], s_sz[PKV_NSUB];       // per sub-block: long / short width, short records, bytes
+    __shared__ uint32_t s_off[PKV_NSUB], s_choff[NCH + 1];                                    // byte offset of a sub-block / of a chunk behind the block's abundance bitmap
+    __shared__ uint32_t s_p, s_wcnt[PK_THREADS / 64];
+    __shared__ unsigned long long s_base, s_pay;
+    const uint32_t g = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    if (t == 0) {                                               // partition of block slot g: the largest p with blk_first[p] <= g
+        uint32_t lo = 0, hi = P.nb;
+        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (P.blk_first[mid] <= g) lo = mid; else hi = mid; }
+        s_p = lo;
+    }
+    for (uint32_t i = t; i < PK_BLOCK / 64; i += PK_THREADS) s_bits[i] = 0ull;
+    if (t < PKV_NSUB) { s_wl[t] = 0u; s_ws[t] = 0u; s_ns[t] = 0u; s_sz[t] = 0u; }
+    if (t < 128) s_hist[t >> 6][t & 63] = 0u;
+    if (t < 2) s_wmax[t] = 0ull;
+    __syncthreads();
+    const uint32_t p = s_p, j = g - P.blk_first[p];
+    const uint64_t s1 = P.ptot[2 * (p + 1) + 1], r0 = P.ptot[2 * p + 1] + (uint64_t)j * PK_BLOCK;
+    const uint32_t n = (uint32_t)min((uint64_t)PK_BLOCK, s1 - r0);
+    if (t == 0) bases[g] = recs[2 * r0];
+    // ---- pass 1 (coalesced), a round = 256 records = 2 sub-blocks (waves 0-1, waves 2-3): the largest delta and the histogram of bit lengths of each -> its two
+    //      widths; the abundance side (bitmap, stream bytes, escapes of abundances >= 255) as in k_pack_counts6
+    uint32_t run = 0;                                           // flagged records of the rounds before this one (the same in every thread)
+    for (uint32_t i0 = 0; i0 < n; i0 += PK_THREADS) {
+        const uint32_t i = i0 + t, sb = wave >> 1;
+        uint32_t ab8 = 1; uint64_t d = 0;
+        if (i < n) {
+            const ulonglong2 me = *reinterpret_cast<const ulonglong2*>(recs + 2 * (r0 + i));
+            const uint64_t prev = i ? recs[2 * (r0 + i - 1)] : me.x;
+            d = me.x - prev;
+            const uint32_t ab = (uint32_t)me.y;
+            ab8 = ab;
+            if (ab >= 255u) {
+                const unsigned long long e = atomicAdd(n_exc, 1ull);
+                if (e < exc_cap) { exc[2 * e] = r0 + i; exc[2 * e + 1] = ab; }
+                ab8 = 255u;
+            }
+            const uint32_t len = d ? 64u - (uint32_t)__clzll((long long)d) : 0u;
+            atomicAdd(&s_hist[sb][len < 63u ? len : 63u], 1u);
+        }
+#pragma unroll
+        for (int d_ = 32; d_ >= 1; d_ >>= 1) { const uint64_t y = (uint64_t)__shfl_xor((unsigned long long)d, d_, 64); d = y > d ? y : d; }
+        if (lane == 0 && d) atomicMax(&s_wmax[sb], (unsigned long long)d);
+        const bool flag = ab8 != 1u;
+        const unsigned long long bal = __ballot(flag);
+        if (lane == 0) { s_bits[(i0 >> 6) + wave] = bal; s_wcnt[wave] = (uint32_t)__popcll(bal); }
+        __syncthreads();
+        uint32_t before = run, total = 0;
+#pragma unroll
+        for (int w = 0; w < PK_THREADS / 64; w++) { if (w < (int)wave) before += s_wcnt[w]; total += s_wcnt[w]; }
+        if (flag) s_cb[before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint8_t)ab8;
+        run += total;
+        if ((wave & 1u) == 0u) {                                // one wave per sub-block: lane L prices the short width L
+            const uint32_t sub = (i0 >> 7) + sb, first = sub * PKV_SUB, cnt = first < n ? min(PKV_SUB, n - first) : 0u;
+            const uint64_t m = s_wmax[sb];
+            uint32_t wl = m ? 64u - (uint32_t)__clzll((long long)m) : 0u;
+            if (wl > 56u) wl = 64u;
+            uint32_t cum = s_hist[sb][lane];                    // records of at most `lane` bits
+#pragma unroll
+            for (int d_ = 1; d_ < 64; d_ <<= 1) { const uint32_t y = __shfl_up(cum, d_, 64); if ((int)lane >= d_) cum += y; }
+            const uint32_t one = (cnt * wl + 7u) >> 3;
+            uint32_t best = lane < wl && lane <= 56u ? ((PKV_SEL + ((cum * lane + 7u) >> 3) + (((cnt - cum) * wl + 7u) >> 3)) << 6) | lane : ~0u;      // (bytes, width): at most 2^11 bytes
+#pragma unroll
+            for (int d_ = 32; d_ >= 1; d_ >>= 1) { const uint32_t y = __shfl_xor(best, d_, 64); best = y < best ? y : best; }
+            const bool split = best != ~0u && (best >> 6) + 16u <= one;
+            const uint32_t ws = split ? best & 63u : wl, ns = __shfl(cum, (int)(best & 63u), 64);
+            if (lane == 0) { s_wl[sub] = wl; s_ws[sub] = ws; s_ns[sub] = split ? ns : 0u; s_sz[sub] = split ? best >> 6 : one; s_wmax[sb] = 0ull; }
+            s_hist[sb][lane] = 0u;
+        }
+        __syncthreads();
+    }
+    if (t < PKV_NSUB) {                                         // (wave 0) the sub-blocks' offsets: a prefix inside every chunk of 16, the chunks padded to 16 bytes
+        const uint32_t sz = s_sz[t];
+        uint32_t x = sz;
+#pragma unroll
+        for (int d_ = 1; d_ < (int)SPC; d_ <<= 1) { const uint32_t y = __shfl_up(x, d_, SPC); if ((int)(lane & (SPC - 1)) >= d_) x += y; }
+        const uint32_t ct = (__shfl(x, (int)(lane | (SPC - 1)), 64) + 15u) & ~15u;
+        uint32_t base = 0, end = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < NCH; c++) { const uint32_t v = __shfl(ct, (int)(c * SPC), 64); if (c < lane / SPC) base += v; end += v; }
+        s_off[t] = base + x - sz;
+        if ((lane & (SPC - 1)) == 0) s_choff[lane / SPC] = base;
+        if (t == 0) s_choff[NCH] = end;
+        wbits[(uint64_t)g * 2 * PKV_NSUB + t] = (uint8_t)s_wl[t];
+        wbits[(uint64_t)g * 2 * PKV_NSUB + PKV_NSUB + t] = (uint8_t)s_ws[t];
+    }
+    __syncthreads();
+    if (t == 0) {
+        const uint64_t bytes = (uint64_t)s_choff[NCH] + PKV_BITMAP;                           // a multiple of 16, at most PKVT_BLOCK_MAX
+        s_pay = atomicAdd(pay_cursor, (unsigned long long)bytes);
+        pay_off16[g] = (uint32_t)(s_pay >> 4);
+        s_base = run ? atomicAdd(cb_cursor, (unsigned long long)run) : 0ull; cb_off[g] = (uint32_t)s_base;
+    }
+    __syncthreads();
+    uint8_t* dstp = payload + s_pay;
+    if (t < PKV_BITMAP / 16) reinterpret_cast<uint4*>(dstp)[t] = reinterpret_cast<const uint4*>(s_bits)[t];      // the abundance bitmap comes FIRST here: 1024 bytes = 64 x 16
+    dstp += PKV_BITMAP;
+    // ---- pass 2 (the block's records again: L2): chunks of 2048 keys through LDS, every thread sends its 8 consecutive deltas to the short or the long stream of its
+    //      sub-block, at the bit its 16-lane prefix of the selector bits says; the chunk (16 sub-blocks back to back, padded to 16 bytes) leaves as 16-byte words
+    auto put = [&](const uint32_t bit, const uint64_t v, const uint32_t w) {                  // v < 2^w at bit `bit` of the zeroed s_out
+        if (!v) return;
+        const uint32_t sh = bit & 63u;
+        atomicOr(&s_out[bit >> 6], (unsigned long long)(v << sh));
+        if (sh + w > 64u) atomicOr(&s_out[(bit >> 6) + 1], (unsigned long long)(v >> (64u - sh)));
+    };
+    for (uint32_t c0 = 0, ch = 0; c0 < n; c0 += PKV_CHUNK, ch++) {
+        const uint32_t cbase = s_choff[ch], cbytes = s_choff[ch + 1] - cbase;                 // (cbytes <= PKVT_CHUNK_MAX)
+        for (uint32_t i = t; i < PKV_CHUNK; i += PK_THREADS) s_key[1 + i] = c0 + i < n ? recs[2 * (r0 + c0 + i)] : 0ull;
+        if (t == 0) s_key[0] = c0 ? recs[2 * (r0 + c0 - 1)] : recs[2 * r0];
+        for (uint32_t w = t; w < (cbytes >> 3) + 2u; w += PK_THREADS) s_out[w] = 0ull;
+        __syncthreads();
+        {
+            const uint32_t sub = ch * SPC + (t >> 4), wl = s_wl[sub], ws = s_ws[sub], ns = s_ns[sub], sbyte = s_off[sub] - cbase;
+            const bool split = ws != wl;
+            uint64_t dl[8]; uint32_t valid = 0, sel = 0;
+            uint64_t prev = s_key[8 * t];
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const uint32_t i = c0 + 8 * t + q;
+                const uint64_t key = s_key[1 + 8 * t + q];
+                dl[q] = i < n ? key - prev : 0ull;
+                prev = key;
+                const uint32_t len = dl[q] ? 64u - (uint32_t)__clzll((long long)dl[q]) : 0u;
+                if (i < n) { valid |= 1u << q; if (!split || len > ws) sel |= 1u << q; }
+            }
+            const uint32_t mine = (uint32_t)__popc(sel) | ((uint32_t)__popc(valid) << 16);
+            uint32_t x = mine;                                  // (long, all) records of the sub-block's threads before this one
+#pragma unroll
+            for (int d_ = 1; d_ < 16; d_ <<= 1) { const uint32_t y = __shfl_up(x, d_, 16); if ((int)(t & 15u) >= d_) x += y; }
+            x -= mine;
+            const uint32_t pl = x & 0xFFFFu, ps = (x >> 16) - pl;
+            uint32_t sbit = 8u * (sbyte + PKV_SEL) + ps * ws;
+            uint32_t lbit = 8u * (sbyte + (split ? PKV_SEL + ((ns * ws + 7u) >> 3) : 0u)) + pl * wl;
+            if (split) put(8u * (sbyte + (t & 15u)), (uint64_t)sel, 8u);
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                if (!((valid >> q) & 1u)) continue;
+                if ((sel >> q) & 1u) { put(lbit, dl[q], wl); lbit += wl; } else { put(sbit, dl[q], ws); sbit += ws; }
+            }
+        }
+        __syncthreads();
+        uint4* dst = reinterpret_cast<uint4*>(dstp + cbase);
+        for (uint32_t w = t; w < (cbytes >> 4); w += PK_THREADS) dst[w] = reinterpret_cast<const uint4*>(s_out)[w];
+        __syncthreads();
+    }
     uint8_t* cb = cb_stream + s_base;
     for (uint32_t i = t; i < run; i += PK_THREADS) cb[i] = s_cb[i];
 }
@@ -403,6 +584,7 @@ struct SinkBatch {
     hipEvent_t copy_start = nullptr;             // GKC_SINK_DEBUG: when the copy stream got to it
     const uint8_t* stage = nullptr;              // [bases: 8 x nblk, padded to 64][payload: nblk x PK_SLOT][exceptions: 16 x n_exc]
     uint64_t nblk = 0, n_exc = 0, pay_off = 0, exc_off = 0; int width = 7;
+    bool two = false;                            // width 6: two delta widths per sub-block (k_pack_counts6t)
     uint64_t cboff_off = 0, cb_off = 0, n_cb = 0;        // width 6: the blocks' offsets into the abundance stream (u32 each), the stream, its length
     uint64_t pay16_off = 0, wbits_off = 0, pay_bytes = 0; // width 6: the blocks' payload offsets (u32, 16-byte units) and bit widths (u8) in the header; bytes of the payload stream
     std::vector<uint64_t> blk_rec0; std::vector<uint32_t> blk_n;       // per block: first record (index in the batch), records
@@ -487,6 +669,129 @@ struct gkc_unpacker {
             pay += 16u * W;
         }
     }
+    // PKV with two widths: the deltas of one stream of a split sub-block (cnt records at W bits from p) into an array, by the same constant-shift groups of 8
+    template <int W> static void pkv_take(const uint8_t* p, const uint32_t cnt, uint64_t* d)
+    {
+        constexpr uint64_t mask = W >= 64 ? ~0ull : ((1ull << (W & 63)) - 1ull);
+        uint32_t i = 0;
+        for (; i + 8 <= cnt; i += 8) {
+            const uint8_t* q = p + (size_t)(i >> 3) * W;
+#pragma unroll
+            for (int j = 0; j < 8; j++) { uint64_t w; memcpy(&w, q + ((j * W) >> 3), 8); d[i + j] = (w >> ((j * W) & 7)) & mask; }      // (up to 7 bytes beyond the group: the next stream / sub-block / padding)
+        }
+        for (uint64_t bit = (uint64_t)i * W; i < cnt; i++, bit += W) { uint64_t w; memcpy(&w, p + (bit >> 3), 8); d[i] = (w >> (bit & 7)) & mask; }
+    }
+    typedef void (*take_fn)(const uint8_t*, uint32_t, uint64_t*);
+    template <size_t... I> static const take_fn* take_table(std::index_sequence<I...>) { static const take_fn t[] = { &pkv_take<(int)I>... }; return t; }
+    // The merge and everything behind it, 8 records at a time, where the host has AVX-512 (every host an MI355X sits in does; the scalar loop below is what is left
+    // without): VPEXPANDQ puts the next short and long deltas at the places the selector byte names, three shifted adds and the carried key make the 8 keys, a
+    // second expansion puts the abundance bytes of the flagged records over the 1s of the others, and two permutes interleave keys and abundances into 8 records.
+    // The expansion threads cannot be more (24 beside the copy stream: more of them expand LESS), so what a record costs a thread is what decides whether the host
+    // keeps up with a link that hands over more records per second; measured per batch of 3.1e8 records: profiles/r07_two_widths.txt.
+    static bool have_avx512() { static const bool ok = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("popcnt"); return ok; }
+#if !defined(__HIP_DEVICE_COMPILE__)
+    __attribute__((target("avx512f,popcnt")))
+    static void pkv_emit512(const SinkBatch& B, const uint64_t* sd, const uint64_t* ld, const uint64_t* sel, const uint32_t cnt, const uint64_t rec0, uint64_t& key_io,
+                            const uint64_t* bits, const uint8_t*& cb_io, __m128i* out)
+    {
+        const __m512i zero = _mm512_setzero_si512(), one = _mm512_set1_epi64(1), esc255 = _mm512_set1_epi64(255), last = _mm512_set1_epi64(7);
+        const __m512i i0 = _mm512_setr_epi64(0, 8, 1, 9, 2, 10, 3, 11), i1 = _mm512_setr_epi64(4, 12, 5, 13, 6, 14, 7, 15);
+        const bool aligned = ((uintptr_t)out & 63) == 0;                              // (8 records = 128 bytes: the same for every group of the sub-block)
+        __m512i carry = _mm512_set1_epi64((long long)key_io);
+        const uint8_t* cb = cb_io;
+        uint32_t si = 0, li = 0, i = 0;
+        for (; i + 8 <= cnt; i += 8) {
+            const __mmask8 m = (__mmask8)(sel[i >> 6] >> (i & 63)), fm = (__mmask8)(bits[i >> 6] >> (i & 63));
+            __m512i x = _mm512_mask_expand_epi64(_mm512_maskz_expand_epi64((__mmask8)~m, _mm512_loadu_si512(sd + si)), m, _mm512_loadu_si512(ld + li));
+            const uint32_t nl = (uint32_t)__builtin_popcount(m); li += nl; si += 8u - nl;
+            x = _mm512_add_epi64(x, _mm512_alignr_epi64(x, zero, 7));
+            x = _mm512_add_epi64(x, _mm512_alignr_epi64(x, zero, 6));
+            x = _mm512_add_epi64(x, _mm512_alignr_epi64(x, zero, 4));
+            x = _mm512_add_epi64(x, carry);
+            carry = _mm512_permutexvar_epi64(last, x);
+            __m512i ab = _mm512_mask_expand_epi64(one, fm, _mm512_cvtepu8_epi64(_mm_loadl_epi64(reinterpret_cast<const __m128i*>(cb))));      // (8 bytes from the cursor: padding follows the stream)
+            cb += __builtin_popcount(fm);
+            const __mmask8 esc = _mm512_cmpeq_epi64_mask(ab, esc255);
+            if (esc) {
+                alignas(64) uint64_t a8[8]; _mm512_store_si512(a8, ab);
+                for (int j = 0; j < 8; j++) if ((esc >> j) & 1) a8[j] = (uint32_t)lookup(B.exc, rec0 + i + j);
+                ab = _mm512_load_si512(a8);
+            }
+            const __m512i lo = _mm512_permutex2var_epi64(x, i0, ab), hi = _mm512_permutex2var_epi64(x, i1, ab);
+            if (aligned) { _mm512_stream_si512(reinterpret_cast<__m512i*>(out + i), lo); _mm512_stream_si512(reinterpret_cast<__m512i*>(out + i + 4), hi); }
+            else {
+                _mm_stream_si128(out + i, _mm512_castsi512_si128(lo)); _mm_stream_si128(out + i + 1, _mm512_extracti32x4_epi32(lo, 1));
+                _mm_stream_si128(out + i + 2, _mm512_extracti32x4_epi32(lo, 2)); _mm_stream_si128(out + i + 3, _mm512_extracti32x4_epi32(lo, 3));
+                _mm_stream_si128(out + i + 4, _mm512_castsi512_si128(hi)); _mm_stream_si128(out + i + 5, _mm512_extracti32x4_epi32(hi, 1));
+                _mm_stream_si128(out + i + 6, _mm512_extracti32x4_epi32(hi, 2)); _mm_stream_si128(out + i + 7, _mm512_extracti32x4_epi32(hi, 3));
+            }
+        }
+        uint64_t key = (uint64_t)_mm_cvtsi128_si64(_mm512_castsi512_si128(carry));
+        for (; i < cnt; i++) {                                                        // the last records of a partition
+            const uint32_t l = (uint32_t)(sel[i >> 6] >> (i & 63)) & 1u, f = (uint32_t)(bits[i >> 6] >> (i & 63)) & 1u;
+            key += l ? ld[li] : sd[si]; li += l; si += 1u - l;
+            uint32_t ab = 1u + f * ((uint32_t)*cb - 1u); cb += f;
+            if (ab == 255u) ab = (uint32_t)lookup(B.exc, rec0 + i);
+            _mm_stream_si128(out + i, _mm_set_epi64x((long long)(uint64_t)ab, (long long)key));
+        }
+        key_io = key; cb_io = cb;
+    }
+#else
+    static void pkv_emit512(const SinkBatch&, const uint64_t*, const uint64_t*, const uint64_t*, uint32_t, uint64_t, uint64_t&, const uint64_t*, const uint8_t*&, __m128i*);
+#endif
+    static void unpack_block_6t(const SinkBatch& B, uint64_t g)                      // PKV, a short and a long delta width per sub-block of 128 records
+    {
+        static const pkv_fn* const table = pkv_table(std::make_index_sequence<65>());
+        static const take_fn* const take = take_table(std::make_index_sequence<65>());
+        const uint64_t r0 = B.blk_rec0[g]; const uint32_t n = B.blk_n[g];
+        const uint8_t* wb = B.stage + B.wbits_off + g * 2 * PKV_NSUB;              // [long widths | short widths]
+        const uint8_t* pay = B.stage + B.pay_off + ((uint64_t)reinterpret_cast<const uint32_t*>(B.stage + B.pay16_off)[g] << 4);
+        const uint64_t* bits = reinterpret_cast<const uint64_t*>(pay);             // the abundance bitmap comes first
+        pay += PKV_BITMAP;
+        const uint8_t* cb = B.stage + B.cb_off + reinterpret_cast<const uint32_t*>(B.stage + B.cboff_off)[g];
+        uint64_t key = reinterpret_cast<const uint64_t*>(B.stage)[g];           // (a block's first delta is 0)
+        __m128i* out = reinterpret_cast<__m128i*>(B.dest + r0 * 16);
+        uint32_t off = 0;
+        const bool fast = have_avx512();
+        for (uint32_t s0 = 0; s0 < n; s0 += PKV_SUB) {
+            const uint32_t s = s0 / PKV_SUB, cnt = std::min<uint32_t>(PKV_SUB, n - s0);
+            const uint32_t wl = std::min<uint32_t>(wb[s], 64u), ws = std::min<uint32_t>(wb[PKV_NSUB + s], 64u);
+            if (fast) {
+                uint64_t sel[2] = { ~0ull, ~0ull }; uint32_t ns = 0, sbytes = 0, skip = 0;
+                if (ws != wl) {
+                    memcpy(sel, pay + off, PKV_SEL);
+                    const uint32_t nl = (uint32_t)(__builtin_popcountll(sel[0]) + __builtin_popcountll(sel[1]));
+                    ns = cnt - std::min(nl, cnt); sbytes = (ns * ws + 7u) >> 3; skip = PKV_SEL;
+                }
+                uint64_t d[2][PKV_SUB + 8];                                         // [0] the short deltas, [1] the long ones
+                if (ns) take[ws](pay + off + skip, ns, d[0]);
+                take[wl](pay + off + skip + sbytes, cnt - ns, d[1]);
+                pkv_emit512(B, d[0], d[1], sel, cnt, r0 + s0, key, bits + (s0 >> 6), cb, out + s0);
+                off += skip + sbytes + (((cnt - ns) * wl + 7u) >> 3);
+            } else if (ws == wl) {                                                         // one width, no selector bitmap: the loop of the one-width format
+                table[wl](B, pay + off, cnt, r0 + s0, key, bits + (s0 >> 6), cb, out + s0);
+                off += (cnt * wl + 7u) >> 3;
+            } else {
+                uint64_t sel[2]; memcpy(sel, pay + off, PKV_SEL);
+                const uint32_t nl = (uint32_t)(__builtin_popcountll(sel[0]) + __builtin_popcountll(sel[1])), ns = cnt - std::min(nl, cnt), sbytes = (ns * ws + 7u) >> 3;
+                uint64_t d[2][PKV_SUB + 8];                                            // [0] the short deltas, [1] the long ones
+                take[ws](pay + off + PKV_SEL, ns, d[0]);
+                take[wl](pay + off + PKV_SEL + sbytes, cnt - ns, d[1]);
+                uint32_t si = 0, li = 0;
+                const uint64_t* fl = bits + (s0 >> 6);
+                for (uint32_t i = 0; i < cnt; i++) {                                // merged by the selector bits while the key runs on
+                    const uint32_t l = (uint32_t)(sel[i >> 6] >> (i & 63)) & 1u, f = (uint32_t)(fl[i >> 6] >> (i & 63)) & 1u;
+                    const uint64_t a = d[0][si], b = d[1][li];                      // (both read, one taken: no branch on a bit that is 1 for two records in three)
+                    key += l ? b : a; li += l; si += 1u - l;
+                    uint32_t ab = 1u + f * ((uint32_t)*cb - 1u); cb += f;
+                    if (ab == 255u) ab = (uint32_t)lookup(B.exc, r0 + s0 + i);
+                    _mm_stream_si128(out + s0 + i, _mm_set_epi64x((long long)(uint64_t)ab, (long long)key));
+                }
+                off += PKV_SEL + sbytes + (((cnt - ns) * wl + 7u) >> 3);
+            }
+            if ((s & (PKV_CHUNK / PKV_SUB - 1)) == PKV_CHUNK / PKV_SUB - 1) off = (off + 15u) & ~15u;      // a pack iteration's 16 sub-blocks are padded to 16 bytes together
+        }
+    }
     static void unpack_block_pkv2(const SinkBatch& B, uint64_t g)                     // PKV, 16-byte keys: 32-byte records {value low, value high, abundance, 0}
     {
         typedef unsigned __int128 u128;
@@ -542,7 +847,7 @@ struct gkc_unpacker {
     }
     static void unpack_block(const SinkBatch& B, uint64_t g)
     {
-        if (B.width == 6) unpack_block_6(B, g); else if (B.width == 14) unpack_block_pkv2(B, g); else if (B.width == 7) unpack_block_w<7>(B, g); else if (B.width == 8) unpack_block_w<8>(B, g);
+        if (B.width == 6) { if (B.two) unpack_block_6t(B, g); else unpack_block_6(B, g); } else if (B.width == 14) unpack_block_pkv2(B, g); else if (B.width == 7) unpack_block_w<7>(B, g); else if (B.width == 8) unpack_block_w<8>(B, g);
         else if (B.width == 16) unpack_block_2<16>(B, g); else unpack_block_2<17>(B, g);
     }
     void worker()
@@ -635,7 +940,12 @@ static gkc_unpacker* unpacker_of(gkc_ctx* c)
     gkc_unpacker* U = new gkc_unpacker(); U->c = c;
     // measured on the 2 x 64-core host of the MI355X box (tools/hostmem_probe/unpack_probe): 16 threads expand 14e9 records/s (100 GB/s read + 230 GB/s of non-temporal
     // writes) with or without a device -> host copy running beside them; 64 threads fall to 6e9/s beside the copy stream, 128 to 4e9/s even alone
-    int n = gkc_tun().unpack_threads > 0 ? gkc_tun().unpack_threads : (int)std::min<unsigned>(24u, std::max(2u, std::thread::hardware_concurrency() / 2));
+    // (round 7: with the AVX-512 emitter a record costs a thread a third of what the scalar loops take, and 16 threads keep ahead of the link with the two-width format
+    //  where 24 of them, beside the copy stream and the Stage-B lanes, had steps in which landed batches piled up and the next ones travelled raw: 12 / 16 / 20 / 24
+    //  threads = 447 / 443 / 441 / 487 ms per step, profiles/r07_two_widths.txt)
+    //  (only where that emitter will run: 8-byte keys at abundance-min 1; the other formats keep their scalar loops and their 24 threads)
+    const unsigned n_alone = gkc_unpacker::have_avx512() && gkc_tun().sink_two_widths && c->key_words == 1 && c->amin <= 1 ? 16u : 24u;
+    int n = gkc_tun().unpack_threads > 0 ? gkc_tun().unpack_threads : (int)std::min<unsigned>(n_alone, std::max(2u, std::thread::hardware_concurrency() / 2));
     // Several ranks of one job share the host (a communicator of W ranks on this context = W processes, taken to be spread evenly over the host's NUMA nodes): the host
     // expands 1.2-1.4e10 records/s in all however many ranks ask, and FEWER threads reach it — 8 ranks x 24 threads get 5.2e9 records/s, 8 x 3 threads 1.33e10 (round 6,
     // tools/hostmem_probe/unpack_ranks_probe on the 2 x 64-core host: profiles/r06_host_unpack_ceiling.txt) — so every rank takes its share of 12 threads per node.
@@ -665,7 +975,9 @@ int gkc_sink_prepare(gkc_ctx* c)
     if (!gkc_sink_packed(c, gkc_tun())) return GKC_OK;
     gkc_unpacker* U = unpacker_of(c);
     U->debug = gkc_tun().sink_debug;
-    const uint64_t want = c->key_words == 1 ? c->sink_cap / 16 * 8 + (uint64_t)c->nb_partitions * (pk_slot(8) + 8) + ((uint64_t)64 << 20)
+    // (8-byte keys: a record's delta is at most 8 bytes in every format; two width bytes per sub-block of the two-width PKV, whole sub-blocks per partition)
+    const uint64_t want = c->key_words == 1 ? c->sink_cap / 16 * 8 + (c->sink_cap / 16 / PKV_SUB + (uint64_t)c->nb_partitions * PKV_NSUB) * 2
+                                                  + (uint64_t)c->nb_partitions * (PKVT_BLOCK_MAX + 8) + ((uint64_t)64 << 20)
                                             : c->sink_cap / 32 * 17 + (uint64_t)c->nb_partitions * (pk_slot(17) + 16) + ((uint64_t)64 << 20);
     if (U->staging_cap < want) {
         if (U->staging) (void)hipHostFree(U->staging);
@@ -778,11 +1090,11 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
     const bool dense = solid_prefix[nb] / std::max<uint32_t>(nb, 1) >= (wide ? std::min<uint64_t>(dense_min, PK2_DENSE) : dense_min);
     const bool pkv_ok = !no6 && !c->sink_no6 && solid_prefix[nb] < (1ull << 32);
     const int width = wide ? (pkv_ok ? 14 : dense ? 16 : 17) : !dense ? 8 : (c->amin <= 1 && pkv_ok) ? 6 : 7;
-    const bool pkv = width == 6 || width == 14;
+    const bool pkv = width == 6 || width == 14, two = width == 6 && tun.sink_two_widths;
     const uint64_t n_rec = solid_prefix[nb];
     const uint64_t bases_bytes = (nblk * (wide ? 16 : 8) + 63) / 64 * 64, cboff_bytes = pkv ? (nblk * 4 + 63) / 64 * 64 : 0;
-    const uint64_t wbits_bytes = pkv ? nblk * PKV_NSUB : 0, hdr_bytes = bases_bytes + 2 * cboff_bytes + wbits_bytes;      // width 6: [bases | abundance-stream offsets | payload offsets | widths]
-    const uint64_t pay_bytes = nblk * pk_slot_of(width) + 64, cb_cap = pkv ? (n_rec + 63) / 64 * 64 : 0;                           // (width 6: the worst case — every block at 64 bits; what is copied is what was used)
+    const uint64_t wbits_bytes = pkv ? nblk * PKV_NSUB * (two ? 2 : 1) : 0, hdr_bytes = bases_bytes + 2 * cboff_bytes + wbits_bytes;      // width 6: [bases | abundance-stream offsets | payload offsets | widths]
+    const uint64_t pay_bytes = nblk * (two ? PKVT_BLOCK_MAX : pk_slot_of(width)) + 64, cb_cap = pkv ? (n_rec + 63) / 64 * 64 : 0;                           // (width 6: the worst case — every block at 64 bits; what is copied is what was used)
     const uint32_t exc_cap = 1u << 20;
     g_sink_why = "no device memory for the packed copy";
     DevBuf d_first; if (c->ensure(d_first, (size_t)(nb + 1) * 4) != GKC_OK) return nullptr;
@@ -797,7 +1109,9 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
            && hipMemsetAsync(d_nexc, 0, 24, st) == hipSuccess;
     if (ok) {
         PackPlan P{ (const uint32_t*)d_first.p, d_ptot, nb };
-        if (width == 6) hipLaunchKernelGGL(k_pack_counts6, dim3((unsigned)nblk), dim3(PK_THREADS), 0, st, (const uint64_t*)d_out, P, (uint64_t*)d_packed, (uint32_t*)(d_packed + bases_bytes),
+        if (two) hipLaunchKernelGGL(k_pack_counts6t, dim3((unsigned)nblk), dim3(PK_THREADS), 0, st, (const uint64_t*)d_out, P, (uint64_t*)d_packed, (uint32_t*)(d_packed + bases_bytes),
+                                    (uint32_t*)(d_packed + bases_bytes + cboff_bytes), d_packed + bases_bytes + 2 * cboff_bytes, d_pay, d_nexc + 2, d_cb, d_nexc + 1, (uint64_t*)d_exc, d_nexc, exc_cap);
+        else if (width == 6) hipLaunchKernelGGL(k_pack_counts6, dim3((unsigned)nblk), dim3(PK_THREADS), 0, st, (const uint64_t*)d_out, P, (uint64_t*)d_packed, (uint32_t*)(d_packed + bases_bytes),
                                            (uint32_t*)(d_packed + bases_bytes + cboff_bytes), d_packed + bases_bytes + 2 * cboff_bytes, d_pay, d_nexc + 2, d_cb, d_nexc + 1, (uint64_t*)d_exc, d_nexc, exc_cap);
         else if (width == 14) hipLaunchKernelGGL(k_pack_pkv2, dim3((unsigned)nblk), dim3(PK_THREADS), 0, st, (const uint64_t*)d_out, P, (uint64_t*)d_packed, (uint32_t*)(d_packed + bases_bytes),
                                                  (uint32_t*)(d_packed + bases_bytes + cboff_bytes), d_packed + bases_bytes + 2 * cboff_bytes, d_pay, d_nexc + 2, d_cb, d_nexc + 1, (uint64_t*)d_exc, d_nexc, exc_cap);
@@ -827,7 +1141,7 @@ void* gkc_sink_send_packed(gkc_ctx* c, const void* d_out, const uint64_t* d_ptot
         B->stage = U->staging + U->staging_used; U->staging_used += (need + 63) / 64 * 64;
         c->sink_wire_bytes += hdr_bytes + pay_used + h_ncb + h_nexc * 16;
     }
-    B->nblk = nblk; B->n_exc = h_nexc; B->width = width; B->pay_off = hdr_bytes; B->cboff_off = bases_bytes; B->cb_off = hdr_bytes + pay_used; B->n_cb = h_ncb;
+    B->nblk = nblk; B->n_exc = h_nexc; B->width = width; B->two = two; B->pay_off = hdr_bytes; B->cboff_off = bases_bytes; B->cb_off = hdr_bytes + pay_used; B->n_cb = h_ncb;
     B->pay16_off = bases_bytes + cboff_bytes; B->wbits_off = bases_bytes + 2 * cboff_bytes; B->pay_bytes = pay_used;
     B->exc_off = hdr_bytes + pay_used + cb_stage; B->dest = h_dest; B->d_packed = d_packed;
     B->blk_rec0.resize(nblk); B->blk_n.resize(nblk);

@@ -867,7 +867,7 @@ def test_packed_sink_escapes_and_block_boundaries(gkc, k, amin):
 
 @pytest.mark.parametrize("k,amin,dense,fixed", [(63, 1, 0, 0), (63, 1, 1, 0), (41, 2, 1, 0), (33, 1, 1, 0), (47, 1, 0, 0), (63, 1, 0, 1), (63, 1, 1, 1), (41, 2, 1, 1), (33, 1, 1, 1)])
 def test_packed_sink_16_byte_keys(gkc, monkeypatch, k, amin, dense, fixed):
-    """k >= 32: the 32-byte Count records {u128 value; i32 abundance; padding} cross PCIe packed as well (csrc/gkc_sink.hip, k_pack_counts2: per block of 8192 records a
+    """k >= 32: the 32-byte Count records {u128 value; i32 abundance; padding} cross PCIe packed as well (csrc/gkc_sink.hip, k_pack_fixed16: per block of 8192 records a
     16-byte base key, then [15- or 16-byte key delta][1-byte abundance] = 16 / 17 bytes instead of 32) and are expanded in the sink by the library's threads: what
     gkc_wait_partition hands out must be byte for byte gkc_partition_counts, and that the oracle's records. `dense` (GKC_SINK_DENSE=1) takes the 15-byte deltas on
     partitions of few records — every gap beyond 2^120 escapes through the two-entry exception path; a read copied 700 times gives abundances >= 255 (escape of

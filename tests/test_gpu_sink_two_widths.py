@@ -1,4 +1,4 @@
-"""The packed result batches with TWO delta widths per sub-block of 128 records (csrc/gkc_sink.hip, k_pack_counts6t / unpack_block_6t): 8-byte keys at abundance-min 1,
+"""The packed result batches with TWO delta widths per sub-block of 128 records (csrc/gkc_sink.hip k_pack_pkv_two_widths / csrc/gkc_wire.hpp unpack_pkv_two_widths): 8-byte keys at abundance-min 1,
 dense partitions. A sub-block travels as [selector bitmap][short deltas][long deltas] where that is at least 16 bytes shorter than its deltas at one width, and as
 those otherwise; GKC_SINK_TWO_WIDTHS=0 keeps one width everywhere. Every case: for every partition, what gkc_wait_partition hands out is byte for byte
 gkc_partition_counts, and that the oracle's records; two passes with one context (the staging buffer and the unpack threads are reused). GKC_SINK_DENSE=1 makes

@@ -1,0 +1,269 @@
+// gkc_graph.hip — exact de Bruijn neighbourhoods of the solid k-mers (include/gkc.h, "graph neighbourhoods").
+//
+// The reference finds the neighbours of a node through a Bloom filter and removes the filter's false positives afterwards (BloomAlgorithm, DebloomMinimizerAlgorithm:
+// contains8 of every solid k-mer; BranchingAlgorithm then takes graph.successors / predecessors of every node and keeps the nodes that are not simple). Here the counted
+// results lie in HBM as ascending Count[] per dataset and any canonical k-mer can be looked up in them exactly (gkc_query.hpp: minimizer -> dataset -> sampled index ->
+// window), so the neighbourhood of a solid k-mer is eight lookups and nothing has to be filtered.
+//
+//   k_graph_masks    : one thread per solid record of the whole result state (flat index in dataset order -> dataset by its QDs::base). The eight neighbours are
+//                      made from the record's value x and ONE reverse complement rx: a right extension is ((x << 2) | j) & mask with reverse complement
+//                      (rx >> 2) | (comp(j) << 2(k-1)), a left extension the mirror image. A neighbour shares k-1 bases with x, so its minimizer is the minimum over the
+//                      k-m m-mers it shares with x and its one new m-mer: the order keys of x's m-mers are computed once (k-m+1 evaluations), the running minimum without
+//                      the first / without the last m-mer kept, and each neighbour adds one evaluation (the order key does not depend on the strand: q_mmer_key takes
+//                      the canonical m-mer, the frequency table is built over canonical m-mers). GR_LOCKSTEP searches advance together like in k_q_reads.
+//   k_graph_topology : from the masks, in = popcount(mask >> 4), out = popcount(mask & 15). <false>: per tile of GR_TILE records the number of branching ones
+//                      (!(in == 1 && out == 1)) and the 5 x 5 table topology[in * 5 + out] (LDS table per workgroup, the dominant (1, 1) cell in a register, flushed once);
+//   k_graph_scan_sums: exclusive prefix of the tile sums by one workgroup (the scheme of the flag scan in gkc_banks.hip);
+//   k_graph_topology<true>: the branching records compacted in flat order (= dataset order, ascending inside a dataset) as Count records.
+// Element indices are 64-bit; grids are capped and the kernels stride.
+#include "gkc_common.hpp"
+#include "gkc_device.hpp"
+#include "gkc_query.hpp"
+
+constexpr int GR_THREADS = 256, GR_PER_THREAD = 4;
+constexpr int GR_TILE = GR_THREADS * GR_PER_THREAD;          // records per tile of the topology kernels
+constexpr int GR_LOCKSTEP = 2;                               // searches a thread advances together (two, more was no better)
+static_assert(8 % GR_LOCKSTEP == 0, "the eight neighbours are searched in groups of GR_LOCKSTEP");
+
+// the dataset a flat record index lies in: the last d with base <= g (an empty dataset shares its base with the next one; g is below the total)
+__device__ __forceinline__ uint32_t gr_dataset_of(const QDs* __restrict__ ds, uint32_t n_ds, uint64_t g)
+{
+    uint32_t lo = 0, hi = n_ds;          // answer in [lo, hi)
+    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (ds[mid].base <= g) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// ------------------------------------------------------------------------------------------------ masks
+template <int KW>
+__global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t n_ds, uint64_t g0, uint64_t n, uint8_t* __restrict__ out)
+{
+    typedef typename KeyT<KW>::type key_t;
+    constexpr int RB = 2 * (int)sizeof(key_t);
+    const uint32_t k = P.k, m = P.m;
+    const key_t kmask = KeyT<KW>::mask(k);
+    const uint32_t top = 2u * (k - 1);                         // bit position of a k-mer's first nucleotide
+    for (uint64_t i = (uint64_t)blockIdx.x * GR_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GR_THREADS) {
+        const uint64_t g = g0 + i;
+        const QDs D = P.ds[gr_dataset_of(P.ds, n_ds, g)];
+        const key_t x = q_load_key<key_t>(D.recs + (g - D.base) * (uint64_t)RB);
+        const key_t rx = KeyT<KW>::revcomp(x, k);
+        // order keys of x's m-mers, first to last: a right extension loses the first one, a left extension the last one
+        uint32_t min_r = P.default_key, min_l = P.default_key;
+        for (uint32_t j = 0; j < P.nb_mm; j++) {
+            const uint32_t key = q_mmer_key(P, (uint32_t)(x >> (2u * (k - m - j))) & P.mmask);
+            if (j != 0) min_r = key < min_r ? key : min_r;
+            if (j + 1 != P.nb_mm) min_l = key < min_l ? key : min_l;
+        }
+        const uint32_t suf = (uint32_t)x & (P.mmask >> 2);                    // the last / the first m-1 nucleotides of x
+        const uint32_t pre = (uint32_t)(x >> (2u * (k - m + 1)));
+        uint32_t res = 0;
+#pragma unroll 1
+        for (uint32_t e0 = 0; e0 < 8; e0 += GR_LOCKSTEP) {
+            bool act[GR_LOCKSTEP], found[GR_LOCKSTEP]; uint32_t d[GR_LOCKSTEP]; key_t key[GR_LOCKSTEP]; uint64_t pos[GR_LOCKSTEP], base[GR_LOCKSTEP];
+            const uint8_t* recs[GR_LOCKSTEP];
+#pragma unroll
+            for (int u = 0; u < GR_LOCKSTEP; u++) {
+                const uint32_t e = e0 + (uint32_t)u, nt = e & 3u;
+                const bool left = e >= 4;
+                const key_t fw = left ? ((x >> 2) | ((key_t)nt << top)) : (((x << 2) | (key_t)nt) & kmask);
+                const key_t rv = left ? (((rx << 2) | (key_t)(nt ^ 2u)) & kmask) : ((rx >> 2) | ((key_t)(nt ^ 2u) << top));
+                key[u] = fw < rv ? fw : rv;                    // Model.hpp:294
+                const uint32_t mk = q_mmer_key(P, left ? ((nt << (2u * (m - 1))) | pre) : ((suf << 2) | nt));
+                const uint32_t shared = left ? min_l : min_r;
+                d[u] = q_dataset_of(P, mk < shared ? mk : shared);
+                act[u] = true;
+            }
+            q_search<key_t, RB, GR_LOCKSTEP>(P, act, d, key, found, pos, recs, base);
+#pragma unroll
+            for (int u = 0; u < GR_LOCKSTEP; u++) res |= (uint32_t)found[u] << (e0 + (uint32_t)u);
+        }
+        out[i] = (uint8_t)res;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ topology, branching nodes
+// exclusive prefix of v over the GR_THREADS threads of the workgroup; *total = sum. s_w: 4 words of LDS, free again on return
+__device__ __forceinline__ uint32_t gr_block_excl(uint32_t v, uint32_t* s_w, uint32_t* total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+    if (lane == 63) s_w[wv] = x;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < GR_THREADS / 64; w++) { const uint32_t s = s_w[w]; if (w < wv) base += s; tot += s; }
+    __syncthreads();
+    *total = tot;
+    return base + x - v;
+}
+// the masks of records i .. i + 3 (i a multiple of 4) as one word, and how many of them exist; the caller's array need not be readable beyond n
+__device__ __forceinline__ uint32_t gr_load4_masks(const uint8_t* __restrict__ f, uint64_t n, uint64_t i, uint32_t* n_valid)
+{
+    static_assert(GR_PER_THREAD == 4, "one 32-bit load per thread");
+    if (i >= n) { *n_valid = 0; return 0u; }
+    if (i + 4 <= n && ((uintptr_t)f & 3) == 0) { *n_valid = 4; return *reinterpret_cast<const uint32_t*>(f + i); }
+    const uint32_t c = n - i < 4 ? (uint32_t)(n - i) : 4u;
+    uint32_t w = 0;
+    for (uint32_t r = 0; r < c; r++) w |= (uint32_t)f[i + r] << (8 * r);
+    *n_valid = c;
+    return w;
+}
+template <int KW, bool GATHER>
+__global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __restrict__ masks, uint64_t n, uint32_t n_tiles, uint32_t* __restrict__ sums,
+                                                                unsigned long long* __restrict__ topo, const uint64_t* __restrict__ offs, const QDs* __restrict__ ds, uint32_t n_ds,
+                                                                uint8_t* __restrict__ records, uint64_t cap)
+{
+    typedef typename KeyT<KW>::type key_t;
+    constexpr int RB = 2 * (int)sizeof(key_t);
+    __shared__ uint32_t s_w[GR_THREADS / 64];
+    __shared__ unsigned long long s_topo[25];
+    if (!GATHER) { if (threadIdx.x < 25) s_topo[threadIdx.x] = 0; __syncthreads(); }
+    unsigned long long n11 = 0;                                // nodes with one predecessor and one successor: nearly all of them
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t i = (uint64_t)t * GR_TILE + (uint64_t)threadIdx.x * GR_PER_THREAD;
+        uint32_t n_valid;
+        const uint32_t w = gr_load4_masks(masks, n, i, &n_valid);
+        uint32_t flag[GR_PER_THREAD], s = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < GR_PER_THREAD; r++) {
+            const uint32_t mk = (w >> (8 * r)) & 255u, in = (uint32_t)__popc(mk >> 4), ou = (uint32_t)__popc(mk & 15u);
+            const bool valid = r < n_valid, simple = in == 1 && ou == 1;
+            flag[r] = valid && !simple; s += flag[r];
+            if (!GATHER && valid) { if (simple) n11++; else atomicAdd(&s_topo[in * 5 + ou], 1ull); }
+        }
+        uint32_t tot;
+        const uint32_t ex = gr_block_excl(s, s_w, &tot);
+        if (!GATHER) { if (threadIdx.x == 0) sums[t] = tot; }
+        else {
+            uint64_t p = offs[t] + ex;
+#pragma unroll
+            for (uint32_t r = 0; r < GR_PER_THREAD; r++) {
+                if (!flag[r]) continue;
+                if (p < cap) {
+                    const uint64_t g = i + r;
+                    const QDs D = ds[gr_dataset_of(ds, n_ds, g)];
+                    const uint8_t* src = D.recs + (g - D.base) * (uint64_t)RB;
+                    const key_t x = q_load_key<key_t>(src);
+                    const unsigned long long ab = (unsigned long long)*reinterpret_cast<const uint32_t*>(src + sizeof(key_t));
+                    uint8_t* dst = records + p * (uint64_t)RB;
+                    if constexpr (KW == 1) store16(dst, (unsigned long long)x, ab);
+                    else { store16(dst, (unsigned long long)x, (unsigned long long)(x >> 64)); store16(dst + 16, ab, 0ull); }
+                }
+                p++;
+            }
+        }
+    }
+    if (!GATHER) {
+#pragma unroll
+        for (int dlt = 32; dlt >= 1; dlt >>= 1) n11 += __shfl_xor(n11, dlt, 64);
+        if ((threadIdx.x & 63) == 0 && n11) atomicAdd(&s_topo[1 * 5 + 1], n11);
+        __syncthreads();
+        if (threadIdx.x < 25 && s_topo[threadIdx.x]) atomicAdd(&topo[threadIdx.x], s_topo[threadIdx.x]);
+    }
+}
+// one workgroup: offs[t] = sums[0] + ... + sums[t - 1], offs[n_tiles] = everything; GR_THREADS sums at a time, the carry in 64 bits
+__global__ __launch_bounds__(GR_THREADS) void k_graph_scan_sums(const uint32_t* __restrict__ sums, uint32_t n_tiles, uint64_t* __restrict__ offs)
+{
+    __shared__ uint32_t s_w[GR_THREADS / 64];
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < n_tiles; base += GR_THREADS) {
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t v = t < n_tiles ? sums[t] : 0u;
+        uint32_t tot;
+        const uint32_t ex = gr_block_excl(v, s_w, &tot);
+        if (t < n_tiles) offs[t] = carry + ex;
+        carry += tot;
+        if (n_tiles - base <= GR_THREADS) break;               // (base + GR_THREADS may wrap at the top of the 32-bit range)
+    }
+    if (threadIdx.x == 0) offs[n_tiles] = carry;
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+static uint64_t gr_total(const gkc_ctx* c) { uint64_t t = 0; for (const Dataset& D : c->datasets) t += D.n_solid; return t; }
+
+// masks of the records [g0, g0 + n) of the flat order into d_masks[0, n); q_prepare has run
+static int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks)
+{
+    ScopedTimer tm(c, "graph_neighbors");
+    QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);
+    const uint32_t n_ds = (uint32_t)c->datasets.size();
+    const dim3 grid(q_grid((n + GR_THREADS - 1) / GR_THREADS)), block(GR_THREADS);
+    if (c->key_words == 1) hipLaunchKernelGGL((k_graph_masks<1>), grid, block, 0, c->stream, P, n_ds, g0, n, d_masks);
+    else                   hipLaunchKernelGGL((k_graph_masks<2>), grid, block, 0, c->stream, P, n_ds, g0, n, d_masks);
+    GKC_HIP(c, hipGetLastError());
+    GKC_HIP(c, hipStreamSynchronize(c->stream));
+    return GKC_OK;
+}
+
+extern "C" {
+
+int gkc_graph_neighbors_solid(gkc_ctx* c, uint8_t* d_masks, uint64_t* n_solid)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_solid) *n_solid = 0;
+    GKC_TRY(q_prepare(c, "gkc_graph_neighbors_solid"));
+    const uint64_t total = gr_total(c);
+    if (n_solid) *n_solid = total;
+    if (!total || !d_masks) return GKC_OK;
+    return gr_masks_run(c, 0, total, d_masks);
+}
+
+int gkc_graph_neighbors_partition(gkc_ctx* c, uint32_t pass, uint32_t part, uint8_t* d_masks, uint64_t* n_solid)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_solid) *n_solid = 0;
+    GKC_TRY(q_prepare(c, "gkc_graph_neighbors_partition"));
+    if (pass >= c->nb_passes || part >= c->nb_partitions) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_neighbors_partition: pass %u / partition %u out of range (%u passes, %u partitions)", pass, part, c->nb_passes, c->nb_partitions);
+    const size_t d = (size_t)part + (size_t)pass * c->nb_partitions;
+    uint64_t g0 = 0; for (size_t j = 0; j < d; j++) g0 += c->datasets[j].n_solid;
+    const uint64_t n = c->datasets[d].n_solid;
+    if (n_solid) *n_solid = n;
+    if (!n || !d_masks) return GKC_OK;
+    return gr_masks_run(c, g0, n, d_masks);
+}
+
+int gkc_graph_branching_solid(gkc_ctx* c, const uint8_t* d_masks, void* d_records, uint64_t cap_records, uint64_t* n_branching, uint64_t* topology)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_branching) *n_branching = 0;
+    if (topology) memset(topology, 0, 25 * sizeof(uint64_t));
+    GKC_TRY(q_prepare(c, "gkc_graph_branching_solid"));
+    const uint64_t total = gr_total(c);
+    if (!total) return GKC_OK;
+    const uint64_t n_tiles64 = (total + GR_TILE - 1) / GR_TILE;
+    if (n_tiles64 >= (1ull << 32)) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_branching_solid: more than 2^32 tiles of %d k-mers", GR_TILE);
+    const uint32_t n_tiles = (uint32_t)n_tiles64, n_ds = (uint32_t)c->datasets.size();
+    DevBuf tmp, d_sums, d_offs, d_topo;
+    if (!d_masks) { GKC_TRY(c->ensure(tmp, (size_t)total)); GKC_TRY(gr_masks_run(c, 0, total, (uint8_t*)tmp.p)); d_masks = (const uint8_t*)tmp.p; }
+    GKC_TRY(c->ensure(d_sums, (size_t)n_tiles * 4)); GKC_TRY(c->ensure(d_offs, ((size_t)n_tiles + 1) * 8)); GKC_TRY(c->ensure(d_topo, 25 * 8));
+    uint64_t n_br = 0, topo[25];
+    {
+        ScopedTimer tm(c, "graph_branching");
+        const QDs* ds = (const QDs*)c->qidx.table.p;
+        const dim3 grid(q_grid(n_tiles)), block(GR_THREADS);
+        const bool wide = c->key_words != 1;
+        GKC_HIP(c, hipMemsetAsync(d_topo.p, 0, 25 * 8, c->stream));
+        if (!wide) hipLaunchKernelGGL((k_graph_topology<1, false>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)d_sums.p, (unsigned long long*)d_topo.p, (const uint64_t*)nullptr, ds, n_ds, (uint8_t*)nullptr, (uint64_t)0);
+        else       hipLaunchKernelGGL((k_graph_topology<2, false>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)d_sums.p, (unsigned long long*)d_topo.p, (const uint64_t*)nullptr, ds, n_ds, (uint8_t*)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(k_graph_scan_sums, dim3(1), block, 0, c->stream, (const uint32_t*)d_sums.p, n_tiles, (uint64_t*)d_offs.p);
+        if (d_records && cap_records) {
+            if (!wide) hipLaunchKernelGGL((k_graph_topology<1, true>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const uint64_t*)d_offs.p, ds, n_ds, (uint8_t*)d_records, cap_records);
+            else       hipLaunchKernelGGL((k_graph_topology<2, true>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const uint64_t*)d_offs.p, ds, n_ds, (uint8_t*)d_records, cap_records);
+        }
+        GKC_HIP(c, hipGetLastError());
+        GKC_HIP(c, hipMemcpyAsync(&n_br, (const uint64_t*)d_offs.p + n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
+        GKC_HIP(c, hipMemcpyAsync(topo, d_topo.p, 25 * 8, hipMemcpyDeviceToHost, c->stream));
+        GKC_HIP(c, hipStreamSynchronize(c->stream));           // the scratch goes back to the pool
+    }
+    if (n_branching) *n_branching = n_br;
+    if (topology) memcpy(topology, topo, sizeof topo);
+    if (d_records && n_br > cap_records) GKC_FAIL(c, GKC_ERR_CAPACITY, "gkc_graph_branching_solid: %llu branching nodes, room for %llu records", (unsigned long long)n_br, (unsigned long long)cap_records);
+    return GKC_OK;
+}
+
+}  // extern "C"

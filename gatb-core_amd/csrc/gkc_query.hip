@@ -16,8 +16,10 @@
 //   k_q_summary: per read n_valid / n_found / min / max / sum of an abundance array, one wave per read.
 // The merged state of a gkc_banks is searched the same way over its bare key array; the found position then indexes the per-bank planes (sum, optionally the rows).
 // Element indices are 64-bit; grids are capped and the kernels stride.
+// The dataset table, the routing (q_mmer_key, q_dataset_of) and the search (q_search) live in gkc_query.hpp: gkc_graph.hip searches the same results.
 #include "gkc_common.hpp"
 #include "gkc_device.hpp"
+#include "gkc_query.hpp"
 
 constexpr int QR_THREADS = 256, QR_PER_THREAD = 16;
 constexpr int QR_TILE = QR_THREADS * QR_PER_THREAD;          // k-mer start positions per tile
@@ -25,92 +27,8 @@ constexpr int QR_HALO_WORDS = 4;                             // 64 bases of look
 constexpr int QR_WORDS = QR_TILE / 16 + QR_HALO_WORDS;       // 16-base words per tile
 constexpr int QR_PAD = 12;                                   // zero words behind the planes: k-mer extraction and the key step read past the halo
 constexpr int QR_LOCKSTEP = 2;                               // searches a thread advances together (measured 1 / 2 / 4 / 8: 234 / 222 / 305 / 278 ms)
-constexpr uint32_t QR_GRID_MAX = 256 * 8;
-constexpr uint32_t Q_MAX_BANKS = 64;
 static_assert(QR_PER_THREAD == 16, "a thread owns one 16-base word of positions");
 #define QMKI(p) ((p) + ((p) >> 4))                            // per-position LDS arrays: lane stride 17 words (see MKI in gkc_scan.hip)
-
-struct QDs { const uint8_t* recs; uint64_t n, idx_off, idx_n, base; };      // device twin of QHostDs + the dataset's samples inside the index
-struct QPlanes { const int32_t* plane[Q_MAX_BANKS]; };
-struct QParams {
-    const uint8_t* bases; uint64_t n_bases; const uint32_t* rsbits; uint64_t n_tiles;
-    uint32_t k, m, nb_mm, mmask, mask_ma1; int freq_mode;
-    const uint32_t* mkey_lut; const uint32_t* key2val; uint32_t default_key;
-    const uint16_t* repart; uint32_t nb_passes, nb_partitions;
-    const QDs* ds; const void* samples; uint64_t stride;
-    int32_t* out; int32_t* vectors; uint32_t nb_banks;
-};
-
-template <typename K> __device__ __forceinline__ K q_load_key(const uint8_t* p) { return *reinterpret_cast<const K*>(p); }
-
-// order key of one m-mer given on the forward strand (A3: LUT semantics, restated like k_sample_exact)
-__device__ __forceinline__ uint32_t q_mmer_key(const QParams& P, uint32_t mf)
-{
-    if (P.freq_mode) return P.mkey_lut[mf];
-    const uint32_t rc = (uint32_t)revcomp64(mf, P.m);
-    const uint32_t cn = mf < rc ? mf : rc;
-    uint32_t a = ~(cn | (cn >> 2));
-    a = (a >> 1) & a & P.mask_ma1;                            // "AA" anywhere but as prefix (KMC2 rule)
-    return a ? P.mmask : cn;
-}
-__device__ __forceinline__ uint32_t q_dataset_of(const QParams& P, uint32_t min_key)
-{
-    const uint32_t value = P.freq_mode ? P.key2val[min_key] : min_key;
-    return (uint32_t)P.repart[value] + (value % P.nb_passes) * P.nb_partitions;
-}
-
-// U searches in lock step. Dataset d[u] is searched for key[u] where act[u]; pos[u] = index of the record inside the dataset when found[u].
-// Phase 1 counts the samples <= key (the samples are the records 0, S, 2S ...): none -> the key is below the dataset's first record; else the key can only be in the window
-// of S records behind the last such sample. Phase 2 finds the last record <= key of that window. `best` follows the largest value <= key seen, so no load is needed to
-// decide found. Lanes / slots that have finished load the first sample of the index (always allocated) and ignore it: the loop body has no divergent branch around a load.
-template <typename K, int RB /* bytes from one record's key to the next */, int U>
-__device__ __forceinline__ void q_search(const QParams& P, const bool (&act)[U], const uint32_t (&d)[U], const K (&key)[U], bool (&found)[U], uint64_t (&pos)[U],
-                                         const uint8_t* (&recs)[U], uint64_t (&base)[U])
-{
-    const uint8_t* dummy = reinterpret_cast<const uint8_t*>(P.samples);
-    const K* ix[U]; uint64_t n[U], lo[U], hi[U]; K best[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        const QDs D = P.ds[act[u] ? d[u] : 0u];
-        recs[u] = D.recs; n[u] = D.n; base[u] = D.base; ix[u] = reinterpret_cast<const K*>(P.samples) + D.idx_off;
-        lo[u] = 0; hi[u] = act[u] ? D.idx_n : 0; best[u] = 0;
-    }
-    for (;;) {
-        bool any = false; K v[U]; uint64_t mid[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const bool a = lo[u] < hi[u]; any = any || a;
-            mid[u] = lo[u] + ((hi[u] - lo[u]) >> 1);
-            v[u] = q_load_key<K>(a ? reinterpret_cast<const uint8_t*>(ix[u] + mid[u]) : dummy);
-        }
-        if (!any) break;
-#pragma unroll
-        for (int u = 0; u < U; u++) if (lo[u] < hi[u]) { if (v[u] <= key[u]) { lo[u] = mid[u] + 1; best[u] = v[u]; } else hi[u] = mid[u]; }
-    }
-    // window: records [w0, w1), record w0 = the last sample <= key. Invariant: record lo <= key (its value in best), record hi > key or hi == w1
-    bool in[U];
-#pragma unroll
-    for (int u = 0; u < U; u++) {
-        in[u] = lo[u] != 0;                                    // (lo = samples <= key; 0 also for an empty dataset / an idle slot)
-        const uint64_t w0 = in[u] ? (lo[u] - 1) * P.stride : 0;
-        const uint64_t w1 = in[u] ? (n[u] - w0 < P.stride ? n[u] : w0 + P.stride) : 0;
-        lo[u] = w0; hi[u] = w1;
-    }
-    for (;;) {
-        bool any = false; K v[U]; uint64_t mid[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const bool a = in[u] && hi[u] - lo[u] > 1; any = any || a;
-            mid[u] = lo[u] + ((hi[u] - lo[u]) >> 1);
-            v[u] = q_load_key<K>(a ? recs[u] + mid[u] * (uint64_t)RB : dummy);
-        }
-        if (!any) break;
-#pragma unroll
-        for (int u = 0; u < U; u++) if (in[u] && hi[u] - lo[u] > 1) { if (v[u] <= key[u]) { lo[u] = mid[u]; best[u] = v[u]; } else hi[u] = mid[u]; }
-    }
-#pragma unroll
-    for (int u = 0; u < U; u++) { found[u] = in[u] && best[u] == key[u]; pos[u] = lo[u]; }
-}
 
 // what a found record answers: its abundance (Count records) or the sum of its counts over the banks (+ the row)
 template <typename K, bool BANKS>
@@ -354,7 +272,7 @@ __global__ __launch_bounds__(256) void k_q_summary(const int32_t* __restrict__ a
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static unsigned q_grid(uint64_t n_blocks) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_blocks, QR_GRID_MAX)); }
+unsigned q_grid(uint64_t n_blocks) { return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_blocks, QR_GRID_MAX)); }
 
 int gkc_query_index_build(gkc_ctx* c, QueryIndex& ix, const std::vector<QHostDs>& ds, uint32_t key_words, bool bare)
 {
@@ -387,7 +305,7 @@ int gkc_query_index_build(gkc_ctx* c, QueryIndex& ix, const std::vector<QHostDs>
     return GKC_OK;
 }
 
-static void q_fill_params(QParams& P, const QueryModel& M, const QueryIndex& ix)
+void q_fill_params(QParams& P, const QueryModel& M, const QueryIndex& ix)
 {
     P.k = M.k; P.m = M.m; P.nb_mm = M.k - M.m + 1;
     P.mmask = (uint32_t)((1ULL << (2 * M.m)) - 1);
@@ -431,7 +349,7 @@ int gkc_query_reads_run(gkc_ctx* c, const QueryModel& M, const QueryIndex& ix, c
 }
 
 // the guards of gkc_release_pass and of the whole-context consumers, then the index over what the context holds NOW
-static int q_prepare(gkc_ctx* c, const char* who)
+int q_prepare(gkc_ctx* c, const char* who)
 {
     if (!c->configured) GKC_FAIL(c, GKC_ERR_ARG, "%s: gkc_configure must be called first", who);
     if (gkc_stage_b_in_flight(c)) GKC_FAIL(c, GKC_ERR_ARG, "%s while gkc_finish_pass_async is in flight (gkc_finish_pass_wait first)", who);
@@ -446,12 +364,13 @@ static int q_prepare(gkc_ctx* c, const char* who)
     for (size_t d = 0; d < sig.size(); d++) sig[d] = {c->datasets[d].d_counts, c->datasets[d].n_solid};
     if (ix.valid && ix.stride == gkc_tun().query_index_stride && ix.epoch == c->pass_epoch && ix.sig == sig) return GKC_OK;
     std::vector<QHostDs> ds(sig.size());
-    for (size_t d = 0; d < sig.size(); d++) ds[d] = QHostDs{sig[d].first, sig[d].second, 0};
+    uint64_t first = 0;                                        // (the abundance queries do not read base; gkc_graph.hip finds the dataset of a flat record index by it)
+    for (size_t d = 0; d < sig.size(); d++) { ds[d] = QHostDs{sig[d].first, sig[d].second, first}; first += sig[d].second; }
     GKC_TRY(gkc_query_index_build(c, ix, ds, c->key_words, false));
     ix.epoch = c->pass_epoch; ix.sig = std::move(sig);
     return GKC_OK;
 }
-static QueryModel q_model_of(const gkc_ctx* c)
+QueryModel q_model_of(const gkc_ctx* c)
 {
     QueryModel M{};
     M.k = c->k; M.m = c->m; M.nb_partitions = c->nb_partitions; M.nb_passes = c->nb_passes; M.key_words = c->key_words;

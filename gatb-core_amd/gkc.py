@@ -32,6 +32,7 @@ SYMBOLS = [
     "gkc_banks_create", "gkc_banks_destroy", "gkc_banks_add", "gkc_banks_evaluate", "gkc_banks_partition_info", "gkc_banks_partition_counts",
     "gkc_banks_partition_vectors", "gkc_banks_partition_counts_device", "gkc_banks_histogram",
     "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
+    "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -191,6 +192,9 @@ def lib():
         "gkc_query_kmers": (C.c_int, [vp, vp, u64, u32, vp]),
         "gkc_query_read_summary_device": (C.c_int, [vp, vp, vp, u64, vp]),
         "gkc_query_banks_reads_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp]),
+        "gkc_graph_neighbors_solid": (C.c_int, [vp, vp, P(u64)]),
+        "gkc_graph_neighbors_partition": (C.c_int, [vp, u32, u32, vp, P(u64)]),
+        "gkc_graph_branching_solid": (C.c_int, [vp, vp, vp, u64, P(u64), vp]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -625,6 +629,68 @@ class Counter:
         torch.cuda.synchronize()
         self.query_read_summary_device(ta.data_ptr(), to.data_ptr(), n, tr.data_ptr())
         return tr.cpu().numpy().view(READ_ABUNDANCE).copy()
+
+    # ---- graph neighbourhoods of the solid k-mers (include/gkc.h, "graph neighbourhoods")
+    def neighbor_masks(self, d_out=None):
+        """one byte per solid k-mer, dataset order: bits 0-3 the solid right extensions, bits 4-7 the solid left extensions (A, C, T, G) -> uint8[n_solid] on the
+        host, or, with ``d_out`` (a device pointer to >= n_solid bytes), written there and n_solid returned"""
+        n = C.c_uint64()
+        if d_out is not None:
+            self._chk(self.L.gkc_graph_neighbors_solid(self.h, d_out, C.byref(n)))
+            return n.value
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+        return self._masks_to_host(n.value, lambda p: self.L.gkc_graph_neighbors_solid(self.h, p, C.byref(n)))
+
+    def neighbor_masks_partition(self, pass_, part):
+        """the masks of one dataset -> uint8[n_solid of the dataset]"""
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_neighbors_partition(self.h, pass_, part, None, C.byref(n)))
+        return self._masks_to_host(n.value, lambda p: self.L.gkc_graph_neighbors_partition(self.h, pass_, part, p, C.byref(n)))
+
+    def _masks_to_host(self, n, call):
+        import torch
+        if not n:
+            return np.zeros(0, np.uint8)
+        t = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(call(t.data_ptr()))
+        return t.cpu().numpy()
+
+    def branching_nodes(self, sort=True, d_masks=None):
+        """the solid k-mers that do not have exactly one solid predecessor and one solid successor -> (lo uint64[], hi uint64[], abundance int32[]) like partition().
+        sort=True: ascending by value, the order of the reference's /branching/nodes (on the host, as the reference sorts); sort=False: dataset order, ascending inside
+        a dataset. d_masks: device pointer to the masks neighbor_masks(d_out) wrote (None: computed here, once)"""
+        import torch
+        keep = None
+        if d_masks is None:
+            n = C.c_uint64()
+            self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+            if n.value:
+                keep = torch.zeros(n.value, dtype=torch.uint8, device="cuda")
+                torch.cuda.synchronize()
+                d_masks = keep.data_ptr()
+                self._chk(self.L.gkc_graph_neighbors_solid(self.h, d_masks, C.byref(n)))
+        nb = C.c_uint64()
+        self._chk(self.L.gkc_graph_branching_solid(self.h, d_masks, None, 0, C.byref(nb), None))
+        words = self.rec_bytes // 8
+        if not nb.value:
+            return np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.int32)
+        t = torch.zeros(nb.value * self.rec_bytes, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_branching_solid(self.h, d_masks, t.data_ptr(), nb.value, C.byref(nb), None))
+        r = t.cpu().numpy().view(np.uint64).reshape(-1, words)
+        lo = r[:, 0].copy(); hi = r[:, 1].copy() if words == 4 else np.zeros(len(r), np.uint64)
+        ab = (r[:, words // 2] & np.uint64(0xFFFFFFFF)).astype(np.int32)
+        if sort:
+            o = np.lexsort((lo, hi))
+            lo, hi, ab = lo[o], hi[o], ab[o]
+        return lo, hi, ab
+
+    def graph_topology(self, d_masks=None):
+        """-> uint64[5, 5]: [in, out] = solid k-mers with that many solid predecessors / successors"""
+        topo = np.zeros(25, np.uint64); nb = C.c_uint64()
+        self._chk(self.L.gkc_graph_branching_solid(self.h, d_masks, None, 0, C.byref(nb), _p(topo)))
+        return topo.reshape(5, 5)
 
 
 def balanced_owner_ranges(weights, world):

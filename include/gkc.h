@@ -188,7 +188,8 @@ int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
  * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
- * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers" */
+ * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers"; of the graph neighbourhoods: "graph_neighbors",
+ * "graph_branching" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -440,6 +441,29 @@ int gkc_query_read_summary_device(gkc_ctx* ctx, const int32_t* d_abund, const ui
  * d_sum[g] as above with the sum over banks; d_vectors (may be NULL): int32[n_bases][nb_banks], row of zeros where d_sum[g] <= 0.
  * Errors are read with gkc_last_error(the context the object was created from). (Named gkc_query_*: the gkc_banks_* exports are a closed list, tests/test_banks_cpu.py.) */
 int gkc_query_banks_reads_device(gkc_banks* b, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, int32_t* d_sum, int32_t* d_vectors);
+
+/* ---- graph neighbourhoods: which of the eight de Bruijn neighbours of every solid k-mer are solid too, exactly -----------------------------------
+ * What the reference gets from BloomAlgorithm + DebloomMinimizerAlgorithm (contains8 of every solid k-mer, then the false positives filtered out) and what
+ * BranchingAlgorithm reads through graph.successors / predecessors: here each neighbour is looked up in the counted results themselves (the search of the
+ * abundance queries above, eight lookups per record), so the answer has no false positives and needs neither filter nor debloom.
+ * One mask byte per solid record, bit order of gkc_bloom_contains8: bits 0-3 the right extensions ((x << 2) | j) & mask, bits 4-7 the left extensions
+ * (x >> 2) | (j << 2(k-1)), j = A, C, T, G = 0..3, x = the record's (canonical) value taken as the forward strand, like the reference's node iterator.
+ * A bit is set if and only if min(neighbour, revcomp(neighbour)) is a record of the results the context holds NOW (inside the solidity window of the count). Self-loops
+ * and, at even k, palindromes get no special case: the sentence above is the whole definition. Parity with the reference's graph is claimed for odd k.
+ * in = popcount(mask >> 4), out = popcount(mask & 15); a node is BRANCHING unless in == 1 and out == 1 (BranchingAlgorithm.cpp: what /branching/nodes holds).
+ * State rules, index life cycle and error reporting are those of the abundance queries. No solid k-mer at all is not an error: GKC_OK, counts 0.
+ * Every rank of a communicator answers from the datasets it holds; the merged state of a gkc_banks is not served.
+ * Timing names of gkc_get_timing: "graph_neighbors", "graph_branching" (the index: "query_index"). */
+/* masks of every solid k-mer of every finished dataset, dataset order (the order of gkc_bloom_query_solid / getSolidKmers());
+ * d_masks: device buffer of >= kmers_nb_solid bytes, or NULL (only *n_solid is reported) */
+int gkc_graph_neighbors_solid(gkc_ctx* ctx, uint8_t* d_masks, uint64_t* n_solid);
+/* the same for ONE dataset (a consumer walking the partitions): n = its n_solid */
+int gkc_graph_neighbors_partition(gkc_ctx* ctx, uint32_t pass, uint32_t part, uint8_t* d_masks, uint64_t* n_solid);
+/* d_masks: what gkc_graph_neighbors_solid wrote, or NULL (computed inside). d_records: device, cap_records Count records in the layout of gkc_partition_counts
+ * (value, the k-mer's abundance, pad bytes zero), or NULL: the branching nodes in dataset order, ascending inside a dataset.
+ * *n_branching is always reported; cap too small: GKC_ERR_CAPACITY, nothing written beyond cap. topology: host u64[25] or NULL, topology[in * 5 + out] = solid k-mers
+ * with that many solid predecessors / successors. */
+int gkc_graph_branching_solid(gkc_ctx* ctx, const uint8_t* d_masks, void* d_records, uint64_t cap_records, uint64_t* n_branching, uint64_t* topology);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

@@ -284,6 +284,14 @@ struct QueryIndex {
     std::vector<std::pair<const void*, uint64_t>> sig;   // ... and where the datasets lay (gkc_gather_results moves them without a new pass)
     void drop() { valid = false; table.release(); samples.release(); }
 };
+// Unitigs (gkc_unitigs.hip): where every solid record of the context stands in its unitig, kept between gkc_graph_unitigs_build and the calls that read it. Describes
+// the results the context held when it was built (epoch, sig as in QueryIndex); dropped when they have changed.
+struct UnitigPlacement {
+    DevBuf unitig, pos, first;            // u64[n]: unitig index << 1 | reversed; u32[n]: position in the path; u64[n_unitigs]: records in the unitigs before this one
+    uint64_t n = 0, n_unitigs = 0, n_bases = 0, n_cycles = 0; bool valid = false;
+    std::vector<uint64_t> epoch; std::vector<std::pair<const void*, uint64_t>> sig;
+    void drop() { valid = false; unitig.release(); pos.release(); first.release(); }
+};
 struct QHostDs { const void* recs; uint64_t n, base; };      // one dataset: its ascending records / keys, how many, and its place in the state's flat order (banks: the planes)
 struct QueryModel {                       // what routes a k-mer to its dataset
     uint32_t k, m, nb_partitions, nb_passes, key_words; int freq_mode; uint32_t default_key;
@@ -356,6 +364,7 @@ struct gkc_ctx {
     double d_hint = 0;                        // solid records per key of the last Stage-B pass (0 = none yet): sizes the next pass's batches
     std::map<std::string, Timing> timing;
     QueryIndex qidx;                          // gkc_query_*: index over the finished datasets
+    UnitigPlacement unitigs;                  // gkc_graph_unitigs_*: the placement of the solid records
     // scratch reused across calls
     DevBuf d_scan_counters;    // u64[2P + 8]
     DevBuf d_rsbits;           // read-start bitmask

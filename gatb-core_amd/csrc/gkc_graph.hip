@@ -5,7 +5,8 @@
 // results lie in HBM as ascending Count[] per dataset and any canonical k-mer can be looked up in them exactly (gkc_query.hpp: minimizer -> dataset -> sampled index ->
 // window), so the neighbourhood of a solid k-mer is eight lookups and nothing has to be filtered.
 //
-//   k_graph_masks    : one thread per solid record of the whole result state (flat index in dataset order -> dataset by its QDs::base). The eight neighbours are
+//   k_graph_masks    : one thread per solid record of the whole result state (flat index in dataset order -> dataset by its QDs::base). The eight neighbours
+//                      (gr_shared_minima / gr_neighbour in gkc_graph.hpp, shared with gkc_unitigs.hip) are
 //                      made from the record's value x and ONE reverse complement rx: a right extension is ((x << 2) | j) & mask with reverse complement
 //                      (rx >> 2) | (comp(j) << 2(k-1)), a left extension the mirror image. A neighbour shares k-1 bases with x, so its minimizer is the minimum over the
 //                      k-m m-mers it shares with x and its one new m-mer: the order keys of x's m-mers are computed once (k-m+1 evaluations), the running minimum without
@@ -16,22 +17,7 @@
 //   k_graph_scan_sums: exclusive prefix of the tile sums by one workgroup (the scheme of the flag scan in gkc_banks.hip);
 //   k_graph_topology<true>: the branching records compacted in flat order (= dataset order, ascending inside a dataset) as Count records.
 // Element indices are 64-bit; grids are capped and the kernels stride.
-#include "gkc_common.hpp"
-#include "gkc_device.hpp"
-#include "gkc_query.hpp"
-
-constexpr int GR_THREADS = 256, GR_PER_THREAD = 4;
-constexpr int GR_TILE = GR_THREADS * GR_PER_THREAD;          // records per tile of the topology kernels
-constexpr int GR_LOCKSTEP = 2;                               // searches a thread advances together (two, more was no better)
-static_assert(8 % GR_LOCKSTEP == 0, "the eight neighbours are searched in groups of GR_LOCKSTEP");
-
-// the dataset a flat record index lies in: the last d with base <= g (an empty dataset shares its base with the next one; g is below the total)
-__device__ __forceinline__ uint32_t gr_dataset_of(const QDs* __restrict__ ds, uint32_t n_ds, uint64_t g)
-{
-    uint32_t lo = 0, hi = n_ds;          // answer in [lo, hi)
-    while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (ds[mid].base <= g) lo = mid; else hi = mid; }
-    return lo;
-}
+#include "gkc_graph.hpp"
 
 // ------------------------------------------------------------------------------------------------ masks
 template <int KW>
@@ -47,13 +33,8 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t 
         const QDs D = P.ds[gr_dataset_of(P.ds, n_ds, g)];
         const key_t x = q_load_key<key_t>(D.recs + (g - D.base) * (uint64_t)RB);
         const key_t rx = KeyT<KW>::revcomp(x, k);
-        // order keys of x's m-mers, first to last: a right extension loses the first one, a left extension the last one
-        uint32_t min_r = P.default_key, min_l = P.default_key;
-        for (uint32_t j = 0; j < P.nb_mm; j++) {
-            const uint32_t key = q_mmer_key(P, (uint32_t)(x >> (2u * (k - m - j))) & P.mmask);
-            if (j != 0) min_r = key < min_r ? key : min_r;
-            if (j + 1 != P.nb_mm) min_l = key < min_l ? key : min_l;
-        }
+        uint32_t min_r, min_l;
+        gr_shared_minima<key_t>(P, x, min_r, min_l);
         const uint32_t suf = (uint32_t)x & (P.mmask >> 2);                    // the last / the first m-1 nucleotides of x
         const uint32_t pre = (uint32_t)(x >> (2u * (k - m + 1)));
         uint32_t res = 0;
@@ -63,14 +44,9 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t 
             const uint8_t* recs[GR_LOCKSTEP];
 #pragma unroll
             for (int u = 0; u < GR_LOCKSTEP; u++) {
-                const uint32_t e = e0 + (uint32_t)u, nt = e & 3u;
-                const bool left = e >= 4;
-                const key_t fw = left ? ((x >> 2) | ((key_t)nt << top)) : (((x << 2) | (key_t)nt) & kmask);
-                const key_t rv = left ? (((rx << 2) | (key_t)(nt ^ 2u)) & kmask) : ((rx >> 2) | ((key_t)(nt ^ 2u) << top));
+                key_t fw, rv;
+                gr_neighbour<key_t>(P, x, rx, kmask, top, suf, pre, min_r, min_l, e0 + (uint32_t)u, fw, rv, d[u]);
                 key[u] = fw < rv ? fw : rv;                    // Model.hpp:294
-                const uint32_t mk = q_mmer_key(P, left ? ((nt << (2u * (m - 1))) | pre) : ((suf << 2) | nt));
-                const uint32_t shared = left ? min_l : min_r;
-                d[u] = q_dataset_of(P, mk < shared ? mk : shared);
                 act[u] = true;
             }
             q_search<key_t, RB, GR_LOCKSTEP>(P, act, d, key, found, pos, recs, base);
@@ -82,34 +58,6 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t 
 }
 
 // ------------------------------------------------------------------------------------------------ topology, branching nodes
-// exclusive prefix of v over the GR_THREADS threads of the workgroup; *total = sum. s_w: 4 words of LDS, free again on return
-__device__ __forceinline__ uint32_t gr_block_excl(uint32_t v, uint32_t* s_w, uint32_t* total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
-    if (lane == 63) s_w[wv] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < GR_THREADS / 64; w++) { const uint32_t s = s_w[w]; if (w < wv) base += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return base + x - v;
-}
-// the masks of records i .. i + 3 (i a multiple of 4) as one word, and how many of them exist; the caller's array need not be readable beyond n
-__device__ __forceinline__ uint32_t gr_load4_masks(const uint8_t* __restrict__ f, uint64_t n, uint64_t i, uint32_t* n_valid)
-{
-    static_assert(GR_PER_THREAD == 4, "one 32-bit load per thread");
-    if (i >= n) { *n_valid = 0; return 0u; }
-    if (i + 4 <= n && ((uintptr_t)f & 3) == 0) { *n_valid = 4; return *reinterpret_cast<const uint32_t*>(f + i); }
-    const uint32_t c = n - i < 4 ? (uint32_t)(n - i) : 4u;
-    uint32_t w = 0;
-    for (uint32_t r = 0; r < c; r++) w |= (uint32_t)f[i + r] << (8 * r);
-    *n_valid = c;
-    return w;
-}
 template <int KW, bool GATHER>
 __global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __restrict__ masks, uint64_t n, uint32_t n_tiles, uint32_t* __restrict__ sums,
                                                                 unsigned long long* __restrict__ topo, const uint64_t* __restrict__ offs, const QDs* __restrict__ ds, uint32_t n_ds,
@@ -181,10 +129,10 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_scan_sums(const uint32_t* 
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static uint64_t gr_total(const gkc_ctx* c) { uint64_t t = 0; for (const Dataset& D : c->datasets) t += D.n_solid; return t; }
+uint64_t gr_total(const gkc_ctx* c) { uint64_t t = 0; for (const Dataset& D : c->datasets) t += D.n_solid; return t; }
 
 // masks of the records [g0, g0 + n) of the flat order into d_masks[0, n); q_prepare has run
-static int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks)
+int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks)
 {
     ScopedTimer tm(c, "graph_neighbors");
     QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);

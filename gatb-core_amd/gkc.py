@@ -33,6 +33,7 @@ SYMBOLS = [
     "gkc_banks_partition_vectors", "gkc_banks_partition_counts_device", "gkc_banks_histogram",
     "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
+    "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -195,6 +196,9 @@ def lib():
         "gkc_graph_neighbors_solid": (C.c_int, [vp, vp, P(u64)]),
         "gkc_graph_neighbors_partition": (C.c_int, [vp, u32, u32, vp, P(u64)]),
         "gkc_graph_branching_solid": (C.c_int, [vp, vp, vp, u64, P(u64), vp]),
+        "gkc_graph_unitigs_build": (C.c_int, [vp, vp, P(u64), P(u64), P(u64)]),
+        "gkc_graph_unitigs_write": (C.c_int, [vp, vp, u64, vp, u64, vp]),
+        "gkc_graph_unitigs_nodes": (C.c_int, [vp, vp, vp]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -691,6 +695,42 @@ class Counter:
         topo = np.zeros(25, np.uint64); nb = C.c_uint64()
         self._chk(self.L.gkc_graph_branching_solid(self.h, d_masks, None, 0, C.byref(nb), _p(topo)))
         return topo.reshape(5, 5)
+
+    # ---- unitigs of the solid k-mers (include/gkc.h, "unitigs")
+    def unitigs_build(self, d_masks=None):
+        """ranks the solid records into unitigs and keeps the placement in the context -> (n_unitigs, n_bases, n_cycles). d_masks: device pointer to the masks
+        neighbor_masks(d_out) wrote (None: computed inside)"""
+        nu, nb, nc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self.L.gkc_graph_unitigs_build(self.h, d_masks, C.byref(nu), C.byref(nb), C.byref(nc)))
+        return nu.value, nb.value, nc.value
+
+    def unitigs_device(self, d_masks=None):
+        """-> (bases uint8[n_bases] ASCII, offsets int64[n_unitigs + 1], kc int64[n_unitigs]) as torch tensors on the device (the 64-bit values are unsigned in the
+        C-ABI and below 2^63 here); bases.data_ptr() / offsets.data_ptr() are the arguments of push_reads_device / query_reads_device"""
+        import torch
+        nu, nb, _ = self.unitigs_build(d_masks)
+        bases = torch.zeros(max(nb, 16), dtype=torch.uint8, device="cuda")
+        offsets = torch.zeros(nu + 1, dtype=torch.int64, device="cuda"); kc = torch.zeros(max(nu, 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_unitigs_write(self.h, bases.data_ptr(), nb, offsets.data_ptr(), nu, kc.data_ptr()))
+        return bases[:nb], offsets, kc[:nu]
+
+    def unitigs(self, d_masks=None):
+        """-> (bases uint8[n_bases], offsets uint64[n_unitigs + 1], kc uint64[n_unitigs]) as numpy: unitig u is bases[offsets[u]: offsets[u + 1]], kc[u] the sum of
+        its k-mers' abundances; numbered by ascending start record"""
+        b, o, kc = self.unitigs_device(d_masks)
+        return b.cpu().numpy(), o.cpu().numpy().view(np.uint64), kc.cpu().numpy().view(np.uint64)
+
+    def unitig_of_records(self):
+        """per solid record, dataset order, from the placement of the last unitigs_build / unitigs -> (unitig index uint64[n], reversed bool[n], pos uint32[n])"""
+        import torch
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+        u = torch.zeros(max(n.value, 1), dtype=torch.int64, device="cuda"); p = torch.zeros(max(n.value, 1), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_unitigs_nodes(self.h, u.data_ptr(), p.data_ptr()))
+        u = u[: n.value].cpu().numpy().view(np.uint64)
+        return u >> np.uint64(1), (u & np.uint64(1)).astype(bool), p[: n.value].cpu().numpy().view(np.uint32)
 
 
 def balanced_owner_ranges(weights, world):

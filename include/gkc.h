@@ -189,7 +189,7 @@ int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
  * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
  * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers"; of the graph neighbourhoods: "graph_neighbors",
- * "graph_branching" */
+ * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -464,6 +464,32 @@ int gkc_graph_neighbors_partition(gkc_ctx* ctx, uint32_t pass, uint32_t part, ui
  * *n_branching is always reported; cap too small: GKC_ERR_CAPACITY, nothing written beyond cap. topology: host u64[25] or NULL, topology[in * 5 + out] = solid k-mers
  * with that many solid predecessors / successors. */
 int gkc_graph_branching_solid(gkc_ctx* ctx, const uint8_t* d_masks, void* d_records, uint64_t cap_records, uint64_t* n_branching, uint64_t* topology);
+
+/* ---- unitigs: the maximal non-branching paths of the solid k-mers glued into sequences, on the device ---------------------------------------------
+ * What the reference's GraphUnitigs (bcalm2) computes on the host from the result file, from the exact neighbour masks above. The records are the solid k-mers of all
+ * finished datasets, flat index i in dataset order (the order of gkc_graph_neighbors_solid), x_i the canonical value taken as the forward strand. A record has two ends:
+ * end 0, the right one (mask bits 0-3), and end 1, the left one (bits 4-7); deg(i, s) = popcount of that nibble.
+ *   arrival: y = a neighbour of x_i, c = min(y, revcomp(y)) = record j. Leaving i by its right end one arrives at end 1 of j if c == y, else at end 0; leaving by
+ *            the left end at end 0 if c == y, else at end 1.
+ *   link   : (i, s) and (j, a) are linked if and only if deg(i, s) == 1, deg(j, a) == 1, j != i, and neither x_i nor y equals its own reverse complement
+ *            (palindromes, even k only: a palindrome is a unitig of its own and nothing links to it). The relation is symmetric.
+ *   unitig : a connected component of the links: a path, or an isolated cycle. A path starts at whichever of its two end records has the smaller flat index and leaves
+ *            it through its linked end; a single record stands forward. A cycle is cut at the left end of its smallest record and starts there, forward. Unitigs are
+ *            numbered by ascending start record. A unitig of L records has L + k - 1 bases: record p of the path stands forward or reverse-complemented as it is
+ *            traversed, consecutive records overlap by k - 1 bases. KC = the sum of the records' abundances (no parity with the header fields of bcalm2 is claimed).
+ * Parity with the reference's unitigs (as a set of canonical sequences) is claimed for odd k, like for the masks.
+ * State rules, index life cycle and error reporting are those of the abundance queries. No solid k-mer at all is not an error: GKC_OK, zeros. The ids of the ranking
+ * are 32-bit: a context with 2^31 or more solid k-mers returns GKC_ERR_CAPACITY. Every rank of a communicator answers from the datasets it holds; the merged state
+ * of a gkc_banks is not served.
+ * Timing names of gkc_get_timing: "graph_links", "graph_rank" (its launch count: the rounds of pointer jumping), "graph_emit". */
+/* builds the placement of every solid record and keeps it in the context (dropped when the results change, like the query index).
+ * d_masks: what gkc_graph_neighbors_solid wrote, or NULL (computed inside). */
+int gkc_graph_unitigs_build(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
+/* d_bases: ASCII ACGT, cap_bases >= n_bases. d_offsets: u64[n_unitigs + 1] (room for cap_unitigs + 1) — exactly the arguments of gkc_push_reads_device /
+ * gkc_query_reads_device. d_kc: u64[n_unitigs] or NULL. Too small: GKC_ERR_CAPACITY, nothing written. GKC_ERR_ARG before a build or after the results changed. */
+int gkc_graph_unitigs_write(gkc_ctx* ctx, char* d_bases, uint64_t cap_bases, uint64_t* d_offsets, uint64_t cap_unitigs, uint64_t* d_kc);
+/* per solid record, flat order; either may be NULL. d_unitig: u64 = unitig index << 1 | reversed. d_pos: u32 = position in the path. */
+int gkc_graph_unitigs_nodes(gkc_ctx* ctx, uint64_t* d_unitig, uint32_t* d_pos);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

@@ -289,8 +289,9 @@ struct QueryIndex {
 struct UnitigPlacement {
     DevBuf unitig, pos, first;            // u64[n]: unitig index << 1 | reversed; u32[n]: position in the path; u64[n_unitigs]: records in the unitigs before this one
     uint64_t n = 0, n_unitigs = 0, n_bases = 0, n_cycles = 0; bool valid = false;
+    uint64_t n_links = 0; bool links_counted = false;      // gkc_graph_unitigs_links: the number of links of this placement, once counted
     std::vector<uint64_t> epoch; std::vector<std::pair<const void*, uint64_t>> sig;
-    void drop() { valid = false; unitig.release(); pos.release(); first.release(); }
+    void drop() { valid = false; links_counted = false; unitig.release(); pos.release(); first.release(); }
 };
 struct QHostDs { const void* recs; uint64_t n, base; };      // one dataset: its ascending records / keys, how many, and its place in the state's flat order (banks: the planes)
 struct QueryModel {                       // what routes a k-mer to its dataset

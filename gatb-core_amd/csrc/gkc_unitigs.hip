@@ -20,6 +20,7 @@
 //                        summed per unitig with 64-bit vector atomics.
 // State ids are 32-bit (n_solid < 2^31), element indices 64-bit; grids are capped and the kernels stride. Scratch comes from the context's pool on c->stream and is
 // synchronised before it goes back.
+// The edges of the compacted graph (gkc_graph_unitigs_links, the L: fields of bcalm2) are at the end of this file: count, scan, fill over the placement kept by the build.
 #include "gkc_graph.hpp"
 
 constexpr uint32_t UT_NONE = 0xFFFFFFFFu;
@@ -354,6 +355,212 @@ int gkc_graph_unitigs_nodes(gkc_ctx* c, uint64_t* d_unitig, uint32_t* d_pos)
     if (d_unitig) GKC_HIP(c, hipMemcpyAsync(d_unitig, U.unitig.p, (size_t)U.n * 8, hipMemcpyDeviceToDevice, c->stream));
     if (d_pos) GKC_HIP(c, hipMemcpyAsync(d_pos, U.pos.p, (size_t)U.n * 4, hipMemcpyDeviceToDevice, c->stream));
     GKC_HIP(c, hipStreamSynchronize(c->stream));
+    return GKC_OK;
+}
+
+}  // extern "C"
+
+// ================================================================================================ links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
+//   k_unitig_link_count   : one thread per record. The record at position 0 of unitig u writes the degree of its outward end to cnt[2 u + 1], the one at position L_u - 1
+//                           to cnt[2 u]; a single-record unitig writes both. Every slot is written exactly once, with its record and end beside the count.
+//   k_unitig_link_tiles   : the sum of every tile of GR_TILE slots; k_unitig_link_scan: exclusive prefix of the tile sums by one workgroup (the scheme of k_unitig_scan);
+//   k_unitig_link_offsets : the exclusive prefix inside the tile on top of the tile's offset -> offsets[2 n_unitigs + 1];
+//   k_unitig_link_fill    : one thread per SLOT, from the record << 1 | end the count kernel left per slot, so that every lane of a wave searches (extremities are
+//                           few among the records). A side builds its four neighbours (gr_shared_minima / gr_neighbour), searches them two at a
+//                           time in lock step, reads the placement of the records found, forms the entries, sorts the four of the slot in registers (empty ones last)
+//                           and stores the first deg of them at offsets[slot]. A neighbour the masks name that is no record (masks of other results) raises *bad.
+constexpr uint32_t UT_INNER = 2u;                              // ut_sides: this end of the record lies inside its path
+// which side of its unitig (0: '+', 1: '-') each end of record i is
+__device__ __forceinline__ void ut_sides(const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ first, uint64_t n, uint64_t n_unitigs,
+                                         uint64_t i, uint64_t& u, uint32_t& side_r, uint32_t& side_l)
+{
+    const uint64_t U = unitig[i];
+    u = U >> 1;
+    const bool rev = U & 1;
+    const uint32_t p = pos[i];
+    side_r = UT_INNER; side_l = UT_INNER;
+    if (p == 0) { if (rev) side_r = 1u; else side_l = 1u; }
+    const uint64_t L = (u + 1 < n_unitigs ? first[u + 1] : n) - first[u];
+    if ((uint64_t)p + 1 == L) { if (rev) side_l = 0u; else side_r = 0u; }
+}
+__global__ __launch_bounds__(256) void k_unitig_link_count(const uint8_t* __restrict__ masks, const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ pos,
+                                                            const uint64_t* __restrict__ first, uint64_t n, uint64_t n_unitigs, uint32_t* __restrict__ cnt,
+                                                            uint32_t* __restrict__ slot_rec)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t u; uint32_t side_r, side_l;
+        ut_sides(unitig, pos, first, n, n_unitigs, i, u, side_r, side_l);
+        if (side_r == UT_INNER && side_l == UT_INNER) continue;
+        const uint32_t mk = masks[i];
+        if (side_r != UT_INNER) { cnt[2 * u + side_r] = (uint32_t)__popc(mk & 15u); slot_rec[2 * u + side_r] = (uint32_t)i << 1; }      // (i < 2^31: the build's guard)
+        if (side_l != UT_INNER) { cnt[2 * u + side_l] = (uint32_t)__popc((mk >> 4) & 15u); slot_rec[2 * u + side_l] = ((uint32_t)i << 1) | 1u; }
+    }
+}
+__global__ __launch_bounds__(GR_THREADS) void k_unitig_link_tiles(const uint32_t* __restrict__ cnt, uint64_t n_slots, uint32_t n_tiles, uint64_t* __restrict__ tile_sum)
+{
+    __shared__ uint64_t s_w[GR_THREADS / 64];
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t i0 = (uint64_t)t * GR_TILE + (uint64_t)threadIdx.x * GR_PER_THREAD;
+        uint64_t sum = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < GR_PER_THREAD; r++) sum += i0 + r < n_slots ? cnt[i0 + r] : 0u;
+        uint64_t tot;
+        gr_block_excl<uint64_t>(sum, s_w, &tot);
+        if (threadIdx.x == 0) tile_sum[t] = tot;
+    }
+}
+// one workgroup: the exclusive prefix of the tile sums in place, [n_tiles] = everything
+__global__ __launch_bounds__(GR_THREADS) void k_unitig_link_scan(uint64_t* __restrict__ tile_sum, uint32_t n_tiles)
+{
+    __shared__ uint64_t s_w[GR_THREADS / 64];
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < n_tiles; base += GR_THREADS) {
+        const uint32_t t = base + threadIdx.x;
+        const uint64_t v = t < n_tiles ? tile_sum[t] : 0ull;
+        uint64_t tot;
+        const uint64_t e = gr_block_excl<uint64_t>(v, s_w, &tot);
+        if (t < n_tiles) tile_sum[t] = carry + e;
+        carry += tot;
+        if (n_tiles - base <= GR_THREADS) break;               // (base + GR_THREADS may wrap at the top of the 32-bit range)
+    }
+    if (threadIdx.x == 0) tile_sum[n_tiles] = carry;
+}
+__global__ __launch_bounds__(GR_THREADS) void k_unitig_link_offsets(const uint32_t* __restrict__ cnt, uint64_t n_slots, uint32_t n_tiles, const uint64_t* __restrict__ tile_off,
+                                                                     uint64_t* __restrict__ offsets)
+{
+    __shared__ uint64_t s_w[GR_THREADS / 64];
+    if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n_slots] = tile_off[n_tiles];
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t i0 = (uint64_t)t * GR_TILE + (uint64_t)threadIdx.x * GR_PER_THREAD;
+        uint32_t v[GR_PER_THREAD]; uint64_t sum = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < GR_PER_THREAD; r++) { v[r] = i0 + r < n_slots ? cnt[i0 + r] : 0u; sum += v[r]; }
+        uint64_t tot;
+        uint64_t o = tile_off[t] + gr_block_excl<uint64_t>(sum, s_w, &tot);
+#pragma unroll
+        for (uint32_t r = 0; r < GR_PER_THREAD; r++) { if (i0 + r < n_slots) offsets[i0 + r] = o; o += v[r]; }
+    }
+}
+__device__ __forceinline__ void ut_order(uint64_t& a, uint64_t& b) { const uint64_t lo = a < b ? a : b, hi = a < b ? b : a; a = lo; b = hi; }
+template <int KW>
+__global__ __launch_bounds__(GR_THREADS) void k_unitig_link_fill(QParams P, uint32_t n_ds, uint64_t n, uint64_t n_slots, const uint8_t* __restrict__ masks,
+                                                                  const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ slot_rec,
+                                                                  const uint64_t* __restrict__ offsets, uint64_t* __restrict__ links, uint32_t* __restrict__ bad)
+{
+    typedef typename KeyT<KW>::type key_t;
+    constexpr int RB = 2 * (int)sizeof(key_t);
+    const uint32_t k = P.k, m = P.m;
+    const key_t kmask = KeyT<KW>::mask(k);
+    const uint32_t top = 2u * (k - 1);
+    for (uint64_t t = (uint64_t)blockIdx.x * GR_THREADS + threadIdx.x; t < n_slots; t += (uint64_t)gridDim.x * GR_THREADS) {
+        const uint32_t sr = slot_rec[t], s = sr & 1u;          // the record whose end s is this side
+        const uint64_t i = sr >> 1;
+        const uint32_t nib = ((uint32_t)masks[i] >> (4u * s)) & 15u;
+        if (!nib) continue;
+        const QDs D = P.ds[gr_dataset_of(P.ds, n_ds, i)];
+        const key_t x = q_load_key<key_t>(D.recs + (i - D.base) * (uint64_t)RB), rx = KeyT<KW>::revcomp(x, k);
+        uint32_t min_r, min_l;
+        gr_shared_minima<key_t>(P, x, min_r, min_l);
+        const uint32_t suf = (uint32_t)x & (P.mmask >> 2), pre = (uint32_t)(x >> (2u * (k - m + 1)));
+        uint64_t e[4];
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {                     // the four neighbours of the end, two searches in lock step at a time
+            bool act[2], found[2]; uint32_t d[2], a[2]; key_t key[2]; uint64_t at[2], base[2]; const uint8_t* recs[2];
+#pragma unroll
+            for (uint32_t q = 0; q < 2; q++) {
+                const uint32_t nt = 2u * h + q;
+                key_t fw, rv;
+                gr_neighbour<key_t>(P, x, rx, kmask, top, suf, pre, min_r, min_l, 4u * s + nt, fw, rv, d[q]);
+                key[q] = fw < rv ? fw : rv;
+                a[q] = fw < rv ? 1u - s : s;                   // the arrival rule of k_unitig_links
+                act[q] = (nib >> nt) & 1u;
+            }
+            q_search<key_t, RB, 2>(P, act, d, key, found, at, recs, base);
+#pragma unroll
+            for (uint32_t q = 0; q < 2; q++) {
+                uint64_t ent = ~0ull;
+                const uint64_t j = base[q] + at[q];
+                if (act[q] && found[q] && j < n) {             // (found: always, with the masks of these results)
+                    const uint64_t V = unitig[j];
+                    const bool begin = a[q] == ((V & 1) ? 0u : 1u);      // one arrives at the outward end of the record at position 0
+                    ent = (V & ~1ull) | (begin ? 0ull : 1ull);
+                } else if (act[q]) *bad = 1u;                  // the host answers GKC_ERR_ARG
+                e[2 * h + q] = ent;
+            }
+        }
+        ut_order(e[0], e[1]); ut_order(e[2], e[3]); ut_order(e[0], e[2]); ut_order(e[1], e[3]); ut_order(e[1], e[2]);
+        const uint64_t off = offsets[t], deg = offsets[t + 1] - off;      // (= popcount(nib): what k_unitig_link_count saw in the same masks)
+#pragma unroll
+        for (uint32_t q = 0; q < 4; q++) if (q < deg) links[off + q] = e[q];
+    }
+}
+
+extern "C" {
+
+int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs, uint64_t* d_links, uint64_t cap_links, uint64_t* n_links)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_links) *n_links = 0;
+    GKC_TRY(ut_require_placement(c, "gkc_graph_unitigs_links"));
+    UnitigPlacement& U = c->unitigs;
+    if (d_links && !d_link_offsets) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: links without offsets (both, or neither to count only)");
+    const uint64_t n = U.n, n_slots = 2 * U.n_unitigs;
+    if (!n) {
+        if (d_link_offsets) { GKC_HIP(c, hipMemsetAsync(d_link_offsets, 0, 8, c->stream)); GKC_HIP(c, hipStreamSynchronize(c->stream)); }
+        return GKC_OK;
+    }
+    if (!d_link_offsets && U.links_counted) { if (n_links) *n_links = U.n_links; return GKC_OK; }      // the sizing call after a count of these results
+    const uint32_t n_tiles = (uint32_t)((n_slots + GR_TILE - 1) / GR_TILE), n_ds = (uint32_t)c->datasets.size();
+    const bool own_masks = !d_masks;
+    DevBuf tmp, d_cnt, d_ts, d_slot;
+    ScopedTimer tm(c, "graph_unitig_links");
+    if (own_masks) GKC_TRY(c->ensure(tmp, (size_t)n));         // every allocation before the first launch: a failure returns with nothing in flight
+    GKC_TRY(c->ensure(d_cnt, (size_t)n_slots * 4)); GKC_TRY(c->ensure(d_ts, ((size_t)n_tiles + 2) * 8)); GKC_TRY(c->ensure(d_slot, (size_t)n_slots * 4));
+    if (own_masks) {
+        const int rc = gr_masks_run(c, 0, n, (uint8_t*)tmp.p);
+        if (rc != GKC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+        d_masks = (const uint8_t*)tmp.p;
+    }
+    const uint64_t* unitig = (const uint64_t*)U.unitig.p; const uint32_t* pos = (const uint32_t*)U.pos.p; const uint64_t* first = (const uint64_t*)U.first.p;
+    uint32_t* cnt = (uint32_t*)d_cnt.p; uint64_t* ts = (uint64_t*)d_ts.p;
+    const dim3 tiles(q_grid(n_tiles)), block(GR_THREADS);
+    uint64_t total = 0;
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n_slots * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_slot.p, 0, (size_t)n_slots * 4, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_unitig_link_count, dim3(q_grid((n + 255) / 256)), dim3(256), 0, c->stream, d_masks, unitig, pos, first, n, U.n_unitigs, cnt, (uint32_t*)d_slot.p);
+        hipLaunchKernelGGL(k_unitig_link_tiles, tiles, block, 0, c->stream, (const uint32_t*)cnt, n_slots, n_tiles, ts);
+        hipLaunchKernelGGL(k_unitig_link_scan, dim3(1), block, 0, c->stream, ts, n_tiles);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, ts + n_tiles, 8, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);     // (also after a failure: the scratch goes back to the pool)
+    GKC_HIP(c, e); GKC_HIP(c, es);
+    if (n_links) *n_links = total;
+    if (own_masks) { U.n_links = total; U.links_counted = true; }      // (masks handed in count once they have been searched without a miss)
+    if (!d_link_offsets) return GKC_OK;
+    if (cap_unitigs < U.n_unitigs || cap_links < total)
+        GKC_FAIL(c, GKC_ERR_CAPACITY, "gkc_graph_unitigs_links: %llu links between %llu unitigs, room for %llu and %llu", (unsigned long long)total, (unsigned long long)U.n_unitigs, (unsigned long long)cap_links, (unsigned long long)cap_unitigs);
+    if (total && !d_links) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: the links are required");
+    uint32_t* d_bad = (uint32_t*)(ts + n_tiles + 1); uint32_t bad = 0;
+    e = hipMemsetAsync(d_bad, 0, 4, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_unitig_link_offsets, tiles, block, 0, c->stream, (const uint32_t*)cnt, n_slots, n_tiles, (const uint64_t*)ts, d_link_offsets);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && total) {
+        QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);
+        const dim3 grid(q_grid((n_slots + GR_THREADS - 1) / GR_THREADS));
+        if (c->key_words == 1) hipLaunchKernelGGL((k_unitig_link_fill<1>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)d_slot.p, (const uint64_t*)d_link_offsets, d_links, d_bad);
+        else                   hipLaunchKernelGGL((k_unitig_link_fill<2>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)d_slot.p, (const uint64_t*)d_link_offsets, d_links, d_bad);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream);
+    }
+    const hipError_t ef = hipStreamSynchronize(c->stream);
+    GKC_HIP(c, e); GKC_HIP(c, ef);
+    if (bad) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: d_masks name a neighbour that is no record of these results (the masks of other results?); the buffers hold no links");
+    U.n_links = total; U.links_counted = true;
     return GKC_OK;
 }
 

@@ -33,7 +33,7 @@ SYMBOLS = [
     "gkc_banks_partition_vectors", "gkc_banks_partition_counts_device", "gkc_banks_histogram",
     "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
-    "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes",
+    "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -199,6 +199,7 @@ def lib():
         "gkc_graph_unitigs_build": (C.c_int, [vp, vp, P(u64), P(u64), P(u64)]),
         "gkc_graph_unitigs_write": (C.c_int, [vp, vp, u64, vp, u64, vp]),
         "gkc_graph_unitigs_nodes": (C.c_int, [vp, vp, vp]),
+        "gkc_graph_unitigs_links": (C.c_int, [vp, vp, vp, u64, vp, u64, P(u64)]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -731,6 +732,62 @@ class Counter:
         self._chk(self.L.gkc_graph_unitigs_nodes(self.h, u.data_ptr(), p.data_ptr()))
         u = u[: n.value].cpu().numpy().view(np.uint64)
         return u >> np.uint64(1), (u & np.uint64(1)).astype(bool), p[: n.value].cpu().numpy().view(np.uint32)
+
+    # ---- links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
+    def unitig_links_device(self, d_masks=None):
+        """the edges of the compacted graph as a CSR over the 2 n_unitigs sides -> (link_offsets int64[2 n_unitigs + 1], links int64[n_links]) as torch tensors on
+        the device: slot 2 u + side (side 0: '+', the end of unitig u; side 1: '-', its begin) holds links[link_offsets[t]: link_offsets[t + 1]], ascending, each
+        v << 1 | (0: one arrives at the begin of v, "v:+"; 1: at its end, "v:-"). Builds the placement first, like unitigs_device."""
+        keep, d_masks = self._masks_once(d_masks)
+        nu, _, _ = self.unitigs_build(d_masks)
+        return self._unitig_links_of_placement(nu, d_masks)
+
+    def _masks_once(self, d_masks):
+        """the masks for a build and the link calls behind it, computed once when none are given -> (the tensor that owns them or None, device pointer or None)"""
+        import torch
+        if d_masks is not None:
+            return None, d_masks
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+        if not n.value:
+            return None, None
+        keep = torch.zeros(n.value, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, keep.data_ptr(), C.byref(n)))
+        return keep, keep.data_ptr()
+
+    def _unitig_links_of_placement(self, nu, d_masks):
+        import torch
+        nl = C.c_uint64()
+        self._chk(self.L.gkc_graph_unitigs_links(self.h, d_masks, None, 0, None, 0, C.byref(nl)))
+        offsets = torch.zeros(2 * nu + 1, dtype=torch.int64, device="cuda"); links = torch.zeros(max(nl.value, 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_unitigs_links(self.h, d_masks, offsets.data_ptr(), nu, links.data_ptr(), nl.value, C.byref(nl)))
+        return offsets, links[: nl.value]
+
+    def unitig_links(self, d_masks=None):
+        """-> (link_offsets uint64[2 n_unitigs + 1], links uint64[n_links]) as numpy, see unitig_links_device"""
+        o, l = self.unitig_links_device(d_masks)
+        return o.cpu().numpy().view(np.uint64), l.cpu().numpy().view(np.uint64)
+
+    def write_unitigs_fasta(self, path, d_masks=None):
+        """the unitigs with their links in the layout of bcalm2 that the reference's GraphUnitigs::load_unitigs parses: per unitig
+        ">u LN:i:<bases> KC:i:<kc> km:f:<kc / records, one decimal>  L:+:v:+- ... L:-:v:+- ..." (the '+' side's links first, each side in slot order), the sequence on
+        the next line. Host code over unitigs() and unitig_links() -> (n_unitigs, n_links)"""
+        keep, d_masks = self._masks_once(d_masks)
+        bases, offs, kc = self.unitigs(d_masks)
+        lo, links = (t.cpu().numpy().view(np.uint64) for t in self._unitig_links_of_placement(len(kc), d_masks))
+        k = self.k
+        text = bases.tobytes().decode()
+        with open(path, "w") as f:
+            for u in range(len(kc)):
+                b0, b1 = int(offs[u]), int(offs[u + 1])
+                fields = ["%d" % u, "LN:i:%d" % (b1 - b0), "KC:i:%d" % int(kc[u]), "km:f:%.1f" % (int(kc[u]) / (b1 - b0 - k + 1))]
+                for side, sign in ((0, "+"), (1, "-")):
+                    for e in links[int(lo[2 * u + side]): int(lo[2 * u + side + 1])]:
+                        fields.append("L:%s:%d:%s" % (sign, int(e) >> 1, "-" if int(e) & 1 else "+"))
+                f.write(">" + " ".join(fields) + "\n" + text[b0:b1] + "\n")
+        return len(kc), len(links)
 
 
 def balanced_owner_ranges(weights, world):

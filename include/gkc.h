@@ -189,7 +189,7 @@ int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
  * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
  * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers"; of the graph neighbourhoods: "graph_neighbors",
- * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit" */
+ * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit", "graph_unitig_links" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -481,7 +481,19 @@ int gkc_graph_branching_solid(gkc_ctx* ctx, const uint8_t* d_masks, void* d_reco
  * State rules, index life cycle and error reporting are those of the abundance queries. No solid k-mer at all is not an error: GKC_OK, zeros. The ids of the ranking
  * are 32-bit: a context with 2^31 or more solid k-mers returns GKC_ERR_CAPACITY. Every rank of a communicator answers from the datasets it holds; the merged state
  * of a gkc_banks is not served.
- * Timing names of gkc_get_timing: "graph_links", "graph_rank" (its launch count: the rounds of pointer jumping), "graph_emit". */
+ * Timing names of gkc_get_timing: "graph_links", "graph_rank" (its launch count: the rounds of pointer jumping), "graph_emit", "graph_unitig_links".
+ *
+ * Links between unitigs (the edges of the compacted graph, bcalm2's L: fields). A unitig u of L records has two SIDES: side 0 ('+') is the outward end of the record at
+ * pos = L - 1 (its right end if the record stands forward, its left end if reversed), side 1 ('-') the outward end of the record at pos = 0 (its left end if forward, its
+ * right end if reversed). A single-record unitig stands forward: side 0 is its right end, side 1 its left end. Slot t = 2 u + side.
+ *   link   : for each bit set in the mask nibble of the outward end s of the side's record i: y = that neighbour, c = min(y, revcomp(y)) = record j, a = the arrival end
+ *            (a = 1 - s if y < revcomp(y), else a = s: the rule of the links above), (v, rev_j) = the placement of j. One arrives at the BEGIN of v if
+ *            a == (rev_j ? 0 : 1): entry v << 1 | 0, "L:+-:v:+"; else at its end: entry v << 1 | 1, "L:+-:v:-". The entries of a slot are in ascending order of that
+ *            64-bit value. No special case for j == i, v == u or palindromes: self-links are links (a cut cycle has L:+:u:+ and L:-:u:-, a hairpin end L:+:u:-, a
+ *            self-loop record such as poly-A links to itself on both sides).
+ * A neighbour reached through a side lies at pos 0 (arriving at a begin) or pos L_v - 1 (arriving at an end) of its unitig. At odd k the entries of a slot are distinct,
+ * the relation is symmetric (slot 2u + su holds (v, mv) <=> slot 2v + (1 - mv) holds (u, 1 - su)) and equals the rule of the reference's LinkTigs.cpp: all (k-1)-overlaps
+ * between unitig extremities. Parity with the reference is claimed for odd k only; at even k the sentences above are the whole definition. */
 /* builds the placement of every solid record and keeps it in the context (dropped when the results change, like the query index).
  * d_masks: what gkc_graph_neighbors_solid wrote, or NULL (computed inside). */
 int gkc_graph_unitigs_build(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
@@ -490,6 +502,14 @@ int gkc_graph_unitigs_build(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* n_un
 int gkc_graph_unitigs_write(gkc_ctx* ctx, char* d_bases, uint64_t cap_bases, uint64_t* d_offsets, uint64_t cap_unitigs, uint64_t* d_kc);
 /* per solid record, flat order; either may be NULL. d_unitig: u64 = unitig index << 1 | reversed. d_pos: u32 = position in the path. */
 int gkc_graph_unitigs_nodes(gkc_ctx* ctx, uint64_t* d_unitig, uint32_t* d_pos);
+/* CSR over the 2 n_unitigs sides. d_link_offsets: u64[2 n_unitigs + 1] (room for 2 cap_unitigs + 1), d_links: u64[n_links] (room for cap_links);
+ * both NULL: only *n_links is reported (kept with the placement once counted: the sizing call is free after that). d_masks: what gkc_graph_neighbors_solid
+ * wrote for THESE results, or NULL (computed inside, on every call that computes). Masks that name a neighbour which is no record of these results: GKC_ERR_ARG
+ * after the search, the buffers then hold no links (masks of other results that happen to name only records cannot be told apart and give their own answer).
+ * Too small: GKC_ERR_CAPACITY, *n_links reported, nothing written. GKC_ERR_ARG before a build or after the results changed.
+ * No solid k-mer: GKC_OK, offsets[0] = 0, *n_links = 0. */
+int gkc_graph_unitigs_links(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs,
+                            uint64_t* d_links, uint64_t cap_links, uint64_t* n_links);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

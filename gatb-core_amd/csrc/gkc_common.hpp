@@ -290,6 +290,7 @@ struct UnitigPlacement {
     DevBuf unitig, pos, first;            // u64[n]: unitig index << 1 | reversed; u32[n]: position in the path; u64[n_unitigs]: records in the unitigs before this one
     uint64_t n = 0, n_unitigs = 0, n_bases = 0, n_cycles = 0; bool valid = false;
     uint64_t n_links = 0; bool links_counted = false;      // gkc_graph_unitigs_links: the number of links of this placement, once counted
+    uint64_t n_alive = 0; bool subset = false;             // gkc_graph_unitigs_build_alive / gkc_graph_tips_remove: the records placed (the others: unitig ~0, pos 0); built over an alive array
     std::vector<uint64_t> epoch; std::vector<std::pair<const void*, uint64_t>> sig;
     void drop() { valid = false; links_counted = false; unitig.release(); pos.release(); first.release(); }
 };

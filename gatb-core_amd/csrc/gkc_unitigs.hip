@@ -20,7 +20,8 @@
 //                        summed per unitig with 64-bit vector atomics.
 // State ids are 32-bit (n_solid < 2^31), element indices 64-bit; grids are capped and the kernels stride. Scratch comes from the context's pool on c->stream and is
 // synchronised before it goes back.
-// The edges of the compacted graph (gkc_graph_unitigs_links, the L: fields of bcalm2) are at the end of this file: count, scan, fill over the placement kept by the build.
+// The edges of the compacted graph (gkc_graph_unitigs_links, the L: fields of bcalm2) follow the unitigs: count, scan, fill over the placement kept by the build; the tip
+// removal (gkc_graph_tips_remove: rounds of build over an alive array, links, flags, kill, mask refresh) is at the end of this file.
 #include "gkc_graph.hpp"
 
 constexpr uint32_t UT_NONE = 0xFFFFFFFFu;
@@ -106,7 +107,8 @@ __global__ __launch_bounds__(256) void k_unitig_cut(const uint4* __restrict__ st
 
 // ------------------------------------------------------------------------------------------------ placement, numbering
 __global__ __launch_bounds__(GR_THREADS) void k_unitig_place(const uint4* __restrict__ st, uint64_t n, uint32_t n_tiles, uint32_t* __restrict__ start_of, uint32_t* __restrict__ pos,
-                                                              uint32_t* __restrict__ len, uint64_t* __restrict__ tile_cnt, uint64_t* __restrict__ tile_len)
+                                                              uint32_t* __restrict__ len, uint64_t* __restrict__ tile_cnt, uint64_t* __restrict__ tile_len,
+                                                              const uint8_t* __restrict__ alive)
 {
     __shared__ uint64_t s_w[GR_THREADS / 64];
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
@@ -116,6 +118,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_unitig_place(const uint4* __rest
         for (uint32_t r = 0; r < GR_PER_THREAD; r++) {
             const uint64_t i = i0 + r;
             if (i >= n) break;
+            if (alive && !alive[i]) { start_of[i] = UT_NONE; pos[i] = 0u; len[i] = 0u; continue; }      // a dead record: of no unitig (start | UT_REV never is UT_NONE: n < 2^31)
             const uint4 a = st[2 * i], b = st[2 * i + 1];      // going right, going left
             const uint32_t start = a.z < b.z ? a.z : b.z;
             const bool fwd = b.z == start;                     // (a single record: both walks end where they begin, it stands forward)
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(256) void k_unitig_assign(const uint32_t* __restric
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t s = start_of[i];
-        unitig[i] = ((uint64_t)index_at[s & ~UT_REV] << 1) | (s >> 31);
+        unitig[i] = s == UT_NONE ? ~0ull : ((uint64_t)index_at[s & ~UT_REV] << 1) | (s >> 31);      // (UT_NONE: a dead record, k_unitig_place)
     }
 }
 
@@ -188,10 +191,11 @@ __global__ __launch_bounds__(256) void k_unitig_emit(const QDs* __restrict__ ds,
     const uint32_t top = 2u * (k - 1);
     if (blockIdx.x == 0 && threadIdx.x == 0) offsets[n_unitigs] = n_bases;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t U = unitig[i], u = U >> 1;
+        if (U == ~0ull) continue;                              // a dead record of a placement over an alive array
         const QDs D = ds[gr_dataset_of(ds, n_ds, i)];
         const uint8_t* src = D.recs + (i - D.base) * (uint64_t)RB;
         const key_t x = q_load_key<key_t>(src);
-        const uint64_t U = unitig[i], u = U >> 1;
         const bool rev = U & 1;
         const uint32_t p = pos[i];
         const uint64_t off = first[u] + u * (uint64_t)(k - 1);
@@ -244,21 +248,32 @@ static int ut_rank(gkc_ctx* c, const uint32_t* link, uint64_t n, uint4* st_a, ui
     return GKC_OK;
 }
 
-extern "C" {
-
-int gkc_graph_unitigs_build(gkc_ctx* c, const uint8_t* d_masks, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles)
+// how many records of alive[0, n) are alive: one atomic per wave
+__global__ __launch_bounds__(256) void k_alive_count(const uint8_t* __restrict__ alive, uint64_t n, unsigned long long* __restrict__ count)
 {
-    gkc_tun_refresh();
-    if (!c) return GKC_ERR_ARG;
-    if (n_unitigs) *n_unitigs = 0;
-    if (n_bases) *n_bases = 0;
-    if (n_cycles) *n_cycles = 0;
-    GKC_TRY(q_prepare(c, "gkc_graph_unitigs_build"));
+    uint64_t mine = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) mine += alive[i] != 0;
+#pragma unroll
+    for (int d = 32; d; d >>= 1) mine += __shfl_down(mine, d, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, (unsigned long long)mine);
+}
+
+// The build behind gkc_graph_unitigs_build (d_alive == NULL: every record) and gkc_graph_unitigs_build_alive / gkc_graph_tips_remove (the records with alive[i] != 0, n_alive
+// of them; d_masks consistent with it: a dead record has mask 0 and no mask names it, so it has no link and the ranking leaves it alone; k_unitig_place gives it no unitig).
+// q_prepare has run.
+static int ut_build(gkc_ctx* c, const char* who, const uint8_t* d_masks, const uint8_t* d_alive, uint64_t n_alive, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles)
+{
     UnitigPlacement& U = c->unitigs;
-    U.drop(); U.n = U.n_unitigs = U.n_bases = U.n_cycles = 0;
+    U.drop(); U.n = U.n_alive = U.n_unitigs = U.n_bases = U.n_cycles = 0; U.subset = d_alive != nullptr;
     const uint64_t n = gr_total(c);
-    if (n >= (1ull << 31)) GKC_FAIL(c, GKC_ERR_CAPACITY, "gkc_graph_unitigs_build: %llu solid k-mers, the states of the ranking are 32-bit (fewer than 2^31 records)", (unsigned long long)n);
-    if (n) {
+    if (n >= (1ull << 31)) GKC_FAIL(c, GKC_ERR_CAPACITY, "%s: %llu solid k-mers, the states of the ranking are 32-bit (fewer than 2^31 records)", who, (unsigned long long)n);
+    if (!d_alive) n_alive = n;
+    if (n && !n_alive) {                                       // every record dead: no unitig; the placement says so per record
+        GKC_TRY(c->ensure(U.unitig, (size_t)n * 8)); GKC_TRY(c->ensure(U.pos, (size_t)n * 4));
+        GKC_HIP(c, hipMemsetAsync(U.unitig.p, 0xFF, (size_t)n * 8, c->stream)); GKC_HIP(c, hipMemsetAsync(U.pos.p, 0, (size_t)n * 4, c->stream));
+        GKC_HIP(c, hipStreamSynchronize(c->stream));
+        U.n = n;
+    } else if (n) {
         const uint32_t n_tiles = (uint32_t)((n + GR_TILE - 1) / GR_TILE), n_ds = (uint32_t)c->datasets.size();
         DevBuf tmp, d_link, d_st_a, d_st_b, d_small, d_start, d_len, d_index, d_tc, d_tl;
         if (!d_masks) { GKC_TRY(c->ensure(tmp, (size_t)n)); GKC_TRY(gr_masks_run(c, 0, n, (uint8_t*)tmp.p)); d_masks = (const uint8_t*)tmp.p; }
@@ -289,17 +304,17 @@ int gkc_graph_unitigs_build(gkc_ctx* c, const uint8_t* d_masks, uint64_t* n_unit
                 GKC_HIP(c, hipGetLastError());
                 GKC_HIP(c, hipMemcpyAsync(&cycles, d_cycles, 8, hipMemcpyDeviceToHost, c->stream));
                 rc = ut_rank(c, link, n, (uint4*)d_st_a.p, (uint4*)d_st_b.p, d_flag, &st, &walking, &rounds);
-                if (rc == GKC_OK && walking) { c->set_error(GKC_ERR_HIP, "gkc_graph_unitigs_build: the ranking did not end after the cycles were cut"); rc = GKC_ERR_HIP; }
+                if (rc == GKC_OK && walking) { c->set_error(GKC_ERR_HIP, "%s: the ranking did not end after the cycles were cut", who); rc = GKC_ERR_HIP; }
             }
             if (rc == GKC_OK) {
                 const dim3 tiles(q_grid(n_tiles)), block(GR_THREADS);
-                hipLaunchKernelGGL(k_unitig_place, tiles, block, 0, c->stream, (const uint4*)st, n, n_tiles, (uint32_t*)d_start.p, (uint32_t*)U.pos.p, (uint32_t*)d_len.p, (uint64_t*)d_tc.p, (uint64_t*)d_tl.p);
+                hipLaunchKernelGGL(k_unitig_place, tiles, block, 0, c->stream, (const uint4*)st, n, n_tiles, (uint32_t*)d_start.p, (uint32_t*)U.pos.p, (uint32_t*)d_len.p, (uint64_t*)d_tc.p, (uint64_t*)d_tl.p, d_alive);
                 hipLaunchKernelGGL(k_unitig_scan, dim3(1), block, 0, c->stream, (uint64_t*)d_tc.p, (uint64_t*)d_tl.p, n_tiles);
                 GKC_HIP(c, hipGetLastError());
                 GKC_HIP(c, hipMemcpyAsync(&totals[0], (const uint64_t*)d_tc.p + n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
                 GKC_HIP(c, hipMemcpyAsync(&totals[1], (const uint64_t*)d_tl.p + n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
                 GKC_HIP(c, hipStreamSynchronize(c->stream));
-                if (totals[0] == 0 || totals[0] > n || totals[1] != n) { c->set_error(GKC_ERR_HIP, "gkc_graph_unitigs_build: %llu unitigs of %llu records over %llu solid k-mers", (unsigned long long)totals[0], (unsigned long long)totals[1], (unsigned long long)n); rc = GKC_ERR_HIP; }
+                if (totals[0] == 0 || totals[0] > n_alive || totals[1] != n_alive) { c->set_error(GKC_ERR_HIP, "%s: %llu unitigs of %llu records over %llu solid k-mers", who, (unsigned long long)totals[0], (unsigned long long)totals[1], (unsigned long long)n_alive); rc = GKC_ERR_HIP; }
             }
             if (rc == GKC_OK) {
                 rc = c->ensure(U.first, (size_t)totals[0] * 8);
@@ -314,13 +329,49 @@ int gkc_graph_unitigs_build(gkc_ctx* c, const uint8_t* d_masks, uint64_t* n_unit
             tm.counts = rounds;                                // "graph_rank" counts the rounds of pointer jumping
         }
         if (rc != GKC_OK) { U.drop(); return rc; }
-        U.n = n; U.n_unitigs = totals[0]; U.n_bases = n + totals[0] * (uint64_t)(c->k - 1); U.n_cycles = cycles;
+        U.n = n; U.n_alive = n_alive; U.n_unitigs = totals[0]; U.n_bases = n_alive + totals[0] * (uint64_t)(c->k - 1); U.n_cycles = cycles;
     }
     U.epoch = c->pass_epoch; U.sig = ut_signature(c); U.valid = true;
     if (n_unitigs) *n_unitigs = U.n_unitigs;
     if (n_bases) *n_bases = U.n_bases;
     if (n_cycles) *n_cycles = U.n_cycles;
     return GKC_OK;
+}
+
+extern "C" {
+
+int gkc_graph_unitigs_build(gkc_ctx* c, const uint8_t* d_masks, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_bases) *n_bases = 0;
+    if (n_cycles) *n_cycles = 0;
+    GKC_TRY(q_prepare(c, "gkc_graph_unitigs_build"));
+    return ut_build(c, "gkc_graph_unitigs_build", d_masks, nullptr, 0, n_unitigs, n_bases, n_cycles);
+}
+
+int gkc_graph_unitigs_build_alive(gkc_ctx* c, const uint8_t* d_masks, const uint8_t* d_alive, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_bases) *n_bases = 0;
+    if (n_cycles) *n_cycles = 0;
+    GKC_TRY(q_prepare(c, "gkc_graph_unitigs_build_alive"));
+    const uint64_t n = gr_total(c);
+    if (n && (!d_masks || !d_alive)) { c->unitigs.drop(); GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_build_alive: the masks and the alive array are required"); }
+    uint64_t n_alive = 0;
+    if (n) {
+        DevBuf d_cnt;
+        GKC_TRY(c->ensure(d_cnt, 8));
+        hipError_t e = hipMemsetAsync(d_cnt.p, 0, 8, c->stream);
+        if (e == hipSuccess) { hipLaunchKernelGGL(k_alive_count, dim3(q_grid((n + 255) / 256)), dim3(256), 0, c->stream, d_alive, n, (unsigned long long*)d_cnt.p); e = hipGetLastError(); }
+        if (e == hipSuccess) e = hipMemcpyAsync(&n_alive, d_cnt.p, 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);  // (also after a failure: the scratch goes back to the pool)
+        GKC_HIP(c, e); GKC_HIP(c, es);
+    }
+    return ut_build(c, "gkc_graph_unitigs_build_alive", d_masks, d_alive, n_alive, n_unitigs, n_bases, n_cycles);
 }
 
 int gkc_graph_unitigs_write(gkc_ctx* c, char* d_bases, uint64_t cap_bases, uint64_t* d_offsets, uint64_t cap_unitigs, uint64_t* d_kc)
@@ -333,7 +384,7 @@ int gkc_graph_unitigs_write(gkc_ctx* c, char* d_bases, uint64_t cap_bases, uint6
         GKC_FAIL(c, GKC_ERR_CAPACITY, "gkc_graph_unitigs_write: %llu unitigs of %llu bases, room for %llu and %llu", (unsigned long long)U.n_unitigs, (unsigned long long)U.n_bases, (unsigned long long)cap_unitigs, (unsigned long long)cap_bases);
     if (!d_offsets || (U.n_bases && !d_bases)) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_write: the bases and the offsets are required");
     ScopedTimer tm(c, "graph_emit");
-    if (!U.n) { GKC_HIP(c, hipMemsetAsync(d_offsets, 0, 8, c->stream)); GKC_HIP(c, hipStreamSynchronize(c->stream)); return GKC_OK; }
+    if (!U.n_unitigs) { GKC_HIP(c, hipMemsetAsync(d_offsets, 0, 8, c->stream)); GKC_HIP(c, hipStreamSynchronize(c->stream)); return GKC_OK; }      // (no record, or none alive)
     if (d_kc) GKC_HIP(c, hipMemsetAsync(d_kc, 0, (size_t)U.n_unitigs * 8, c->stream));
     const QDs* ds = (const QDs*)c->qidx.table.p;
     const uint32_t n_ds = (uint32_t)c->datasets.size();
@@ -371,25 +422,27 @@ int gkc_graph_unitigs_nodes(gkc_ctx* c, uint64_t* d_unitig, uint32_t* d_pos)
 //                           and stores the first deg of them at offsets[slot]. A neighbour the masks name that is no record (masks of other results) raises *bad.
 constexpr uint32_t UT_INNER = 2u;                              // ut_sides: this end of the record lies inside its path
 // which side of its unitig (0: '+', 1: '-') each end of record i is
-__device__ __forceinline__ void ut_sides(const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ first, uint64_t n, uint64_t n_unitigs,
+// (n_alive: the records placed, all of them unless the placement was built over an alive array; a dead record, unitig ~0, has no side)
+__device__ __forceinline__ void ut_sides(const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ first, uint64_t n_alive, uint64_t n_unitigs,
                                          uint64_t i, uint64_t& u, uint32_t& side_r, uint32_t& side_l)
 {
     const uint64_t U = unitig[i];
+    side_r = UT_INNER; side_l = UT_INNER;
+    if (U == ~0ull) { u = 0; return; }
     u = U >> 1;
     const bool rev = U & 1;
     const uint32_t p = pos[i];
-    side_r = UT_INNER; side_l = UT_INNER;
     if (p == 0) { if (rev) side_r = 1u; else side_l = 1u; }
-    const uint64_t L = (u + 1 < n_unitigs ? first[u + 1] : n) - first[u];
+    const uint64_t L = (u + 1 < n_unitigs ? first[u + 1] : n_alive) - first[u];
     if ((uint64_t)p + 1 == L) { if (rev) side_l = 0u; else side_r = 0u; }
 }
 __global__ __launch_bounds__(256) void k_unitig_link_count(const uint8_t* __restrict__ masks, const uint64_t* __restrict__ unitig, const uint32_t* __restrict__ pos,
-                                                            const uint64_t* __restrict__ first, uint64_t n, uint64_t n_unitigs, uint32_t* __restrict__ cnt,
+                                                            const uint64_t* __restrict__ first, uint64_t n, uint64_t n_alive, uint64_t n_unitigs, uint32_t* __restrict__ cnt,
                                                             uint32_t* __restrict__ slot_rec)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t u; uint32_t side_r, side_l;
-        ut_sides(unitig, pos, first, n, n_unitigs, i, u, side_r, side_l);
+        ut_sides(unitig, pos, first, n_alive, n_unitigs, i, u, side_r, side_l);
         if (side_r == UT_INNER && side_l == UT_INNER) continue;
         const uint32_t mk = masks[i];
         if (side_r != UT_INNER) { cnt[2 * u + side_r] = (uint32_t)__popc(mk & 15u); slot_rec[2 * u + side_r] = (uint32_t)i << 1; }      // (i < 2^31: the build's guard)
@@ -480,7 +533,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_unitig_link_fill(QParams P, uint
             for (uint32_t q = 0; q < 2; q++) {
                 uint64_t ent = ~0ull;
                 const uint64_t j = base[q] + at[q];
-                if (act[q] && found[q] && j < n) {             // (found: always, with the masks of these results)
+                if (act[q] && found[q] && j < n && unitig[j] != ~0ull) {      // (found, and alive: always, with the masks of these results and of this alive array)
                     const uint64_t V = unitig[j];
                     const bool begin = a[q] == ((V & 1) ? 0u : 1u);      // one arrives at the outward end of the record at position 0
                     ent = (V & ~1ull) | (begin ? 0ull : 1ull);
@@ -495,18 +548,14 @@ __global__ __launch_bounds__(GR_THREADS) void k_unitig_link_fill(QParams P, uint
     }
 }
 
-extern "C" {
-
-int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs, uint64_t* d_links, uint64_t cap_links, uint64_t* n_links)
+// gkc_graph_unitigs_links behind its guards. d_keep_slots (gkc_graph_tips_remove; u32[2 n_unitigs] or NULL): where the record << 1 | end of every slot stays for the caller
+static int ut_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs, uint64_t* d_links, uint64_t cap_links, uint64_t* n_links, uint32_t* d_keep_slots)
 {
-    gkc_tun_refresh();
-    if (!c) return GKC_ERR_ARG;
-    if (n_links) *n_links = 0;
-    GKC_TRY(ut_require_placement(c, "gkc_graph_unitigs_links"));
     UnitigPlacement& U = c->unitigs;
     if (d_links && !d_link_offsets) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: links without offsets (both, or neither to count only)");
+    if (U.subset && !d_masks) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: the placement was built over an alive array, the masks that went with it are required");
     const uint64_t n = U.n, n_slots = 2 * U.n_unitigs;
-    if (!n) {
+    if (!n_slots) {                                            // no record, or none alive
         if (d_link_offsets) { GKC_HIP(c, hipMemsetAsync(d_link_offsets, 0, 8, c->stream)); GKC_HIP(c, hipStreamSynchronize(c->stream)); }
         return GKC_OK;
     }
@@ -516,7 +565,9 @@ int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link
     DevBuf tmp, d_cnt, d_ts, d_slot;
     ScopedTimer tm(c, "graph_unitig_links");
     if (own_masks) GKC_TRY(c->ensure(tmp, (size_t)n));         // every allocation before the first launch: a failure returns with nothing in flight
-    GKC_TRY(c->ensure(d_cnt, (size_t)n_slots * 4)); GKC_TRY(c->ensure(d_ts, ((size_t)n_tiles + 2) * 8)); GKC_TRY(c->ensure(d_slot, (size_t)n_slots * 4));
+    GKC_TRY(c->ensure(d_cnt, (size_t)n_slots * 4)); GKC_TRY(c->ensure(d_ts, ((size_t)n_tiles + 2) * 8));
+    if (!d_keep_slots) GKC_TRY(c->ensure(d_slot, (size_t)n_slots * 4));
+    uint32_t* slot_rec = d_keep_slots ? d_keep_slots : (uint32_t*)d_slot.p;
     if (own_masks) {
         const int rc = gr_masks_run(c, 0, n, (uint8_t*)tmp.p);
         if (rc != GKC_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
@@ -527,9 +578,9 @@ int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link
     const dim3 tiles(q_grid(n_tiles)), block(GR_THREADS);
     uint64_t total = 0;
     hipError_t e = hipMemsetAsync(cnt, 0, (size_t)n_slots * 4, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_slot.p, 0, (size_t)n_slots * 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(slot_rec, 0, (size_t)n_slots * 4, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_unitig_link_count, dim3(q_grid((n + 255) / 256)), dim3(256), 0, c->stream, d_masks, unitig, pos, first, n, U.n_unitigs, cnt, (uint32_t*)d_slot.p);
+        hipLaunchKernelGGL(k_unitig_link_count, dim3(q_grid((n + 255) / 256)), dim3(256), 0, c->stream, d_masks, unitig, pos, first, n, U.n_alive, U.n_unitigs, cnt, slot_rec);
         hipLaunchKernelGGL(k_unitig_link_tiles, tiles, block, 0, c->stream, (const uint32_t*)cnt, n_slots, n_tiles, ts);
         hipLaunchKernelGGL(k_unitig_link_scan, dim3(1), block, 0, c->stream, ts, n_tiles);
         e = hipGetLastError();
@@ -552,8 +603,8 @@ int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link
     if (e == hipSuccess && total) {
         QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);
         const dim3 grid(q_grid((n_slots + GR_THREADS - 1) / GR_THREADS));
-        if (c->key_words == 1) hipLaunchKernelGGL((k_unitig_link_fill<1>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)d_slot.p, (const uint64_t*)d_link_offsets, d_links, d_bad);
-        else                   hipLaunchKernelGGL((k_unitig_link_fill<2>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)d_slot.p, (const uint64_t*)d_link_offsets, d_links, d_bad);
+        if (c->key_words == 1) hipLaunchKernelGGL((k_unitig_link_fill<1>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)slot_rec, (const uint64_t*)d_link_offsets, d_links, d_bad);
+        else                   hipLaunchKernelGGL((k_unitig_link_fill<2>), grid, block, 0, c->stream, P, n_ds, n, n_slots, d_masks, unitig, (const uint32_t*)slot_rec, (const uint64_t*)d_link_offsets, d_links, d_bad);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream);
     }
@@ -561,6 +612,243 @@ int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link
     GKC_HIP(c, e); GKC_HIP(c, ef);
     if (bad) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_unitigs_links: d_masks name a neighbour that is no record of these results (the masks of other results?); the buffers hold no links");
     U.n_links = total; U.links_counted = true;
+    return GKC_OK;
+}
+
+extern "C" {
+
+int gkc_graph_unitigs_links(gkc_ctx* c, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs, uint64_t* d_links, uint64_t cap_links, uint64_t* n_links)
+{
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_links) *n_links = 0;
+    GKC_TRY(ut_require_placement(c, "gkc_graph_unitigs_links"));
+    return ut_links(c, d_masks, d_link_offsets, cap_unitigs, d_links, cap_links, n_links, nullptr);
+}
+
+}  // extern "C"
+
+// ================================================================================================ tips (include/gkc.h, "tips": candidate, tip, competitor, round)
+// A round works on the placement and the link CSR of the alive records:
+//   k_tip_kc      : one thread per record: the abundance sums KC of the unitigs (64-bit vector atomics; the emit kernel's sum without the bases).
+//   k_tip_flags   : one thread per unitig: the degrees of its two slots from the link offsets, its length from first[], the topological rule; for the coverage rule the
+//                   entries of its linked slot and of the arrival slot of each (at most five slots), every comparison in 128-bit integers. One flag byte per unitig.
+//   k_tip_mark    : one thread per slot of a SURVIVING unitig: a slot with an entry whose unitig is flagged goes on a work list (side-0 slots from the front of the list,
+//                   side-1 slots from its back: a single-record unitig has both sides in one mask byte, and each list is refreshed by a launch of its own).
+//   k_tip_kill    : one thread per record: the records of flagged unitigs die, alive[i] = 0, masks[i] = 0.
+//   k_tip_refresh : one thread per listed slot, so that nearly every lane searches (extremities are few among the records). For each bit of the
+//                   outward nibble of the slot's record the neighbour is built and searched as in k_unitig_link_fill; the bit of a neighbour that has died is cleared.
+//                   Only extremities name records of other unitigs, so no other mask changes. A neighbour that is no record raises *bad.
+struct TipRule { uint32_t k, max_len_topo, max_len_rc, rc_num, rc_den; };
+struct TipCounters { unsigned long long n_tips, n_removed; uint32_t n_work[2], bad, pad; };      // one device word block per round
+
+template <int KW>
+__global__ __launch_bounds__(256) void k_tip_kc(const QDs* __restrict__ ds, uint32_t n_ds, uint64_t n, const uint64_t* __restrict__ unitig, unsigned long long* __restrict__ kc)
+{
+    typedef typename KeyT<KW>::type key_t;
+    constexpr int RB = 2 * (int)sizeof(key_t);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t U = unitig[i];
+        if (U == ~0ull) continue;
+        const QDs D = ds[gr_dataset_of(ds, n_ds, i)];
+        atomicAdd(&kc[U >> 1], (unsigned long long)*reinterpret_cast<const uint32_t*>(D.recs + (i - D.base) * (uint64_t)RB + sizeof(key_t)));
+    }
+}
+// "c is that much better covered than u": KC_c L_u rc_den > rc_num KC_u L_c, exactly (KC < 2^63, L < 2^31, the ratio's terms < 2^32: the products stay below 2^126)
+__device__ __forceinline__ bool ut_better_covered(const TipRule& R, uint64_t kc_c, uint64_t len_c, uint64_t kc_u, uint64_t len_u)
+{
+    return (unsigned __int128)kc_c * (unsigned __int128)(len_u * R.rc_den) > (unsigned __int128)kc_u * (unsigned __int128)(len_c * R.rc_num);
+}
+__device__ __forceinline__ uint64_t ut_length(const uint64_t* __restrict__ first, uint64_t n_alive, uint64_t n_unitigs, uint64_t u) { return (u + 1 < n_unitigs ? first[u + 1] : n_alive) - first[u]; }
+__global__ __launch_bounds__(256) void k_tip_flags(TipRule R, uint64_t n_unitigs, uint64_t n_alive, const uint64_t* __restrict__ first, const uint64_t* __restrict__ loff,
+                                                    const uint64_t* __restrict__ links, const unsigned long long* __restrict__ kc, uint8_t* __restrict__ flag, TipCounters* __restrict__ cnt)
+{
+    for (uint64_t u = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; u < n_unitigs; u += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t o0 = loff[2 * u], o1 = loff[2 * u + 1], o2 = loff[2 * u + 2];
+        bool tip = false;
+        if ((o1 == o0) != (o2 == o1)) {                        // a candidate: exactly one side without a link
+            const uint32_t su = o1 != o0 ? 0u : 1u;
+            const uint64_t len_u = ut_length(first, n_alive, n_unitigs, u), bases = len_u + R.k - 1;
+            tip = bases <= R.max_len_topo;
+            if (!tip && bases <= R.max_len_rc) {
+                const uint64_t kc_u = kc[u], back = (u << 1) | (1u - su);
+                const uint64_t b = su ? o1 : o0, e = su ? o2 : o1;
+                for (uint64_t q = b; q < e && !tip; q++) {     // the entries (v, m) of the linked slot: at most four
+                    const uint64_t ent = links[q], v = ent >> 1;
+                    tip = ut_better_covered(R, kc[v], ut_length(first, n_alive, n_unitigs, v), kc_u, len_u);
+                    const uint64_t t2 = 2 * v + (1u - (uint32_t)(ent & 1));      // the slot one arrives through: its other entries are u's siblings
+                    bool skipped = false;
+                    for (uint64_t p = loff[t2], pe = loff[t2 + 1]; p < pe && !tip; p++) {
+                        const uint64_t w = links[p];
+                        if (!skipped && w == back) { skipped = true; continue; }      // the one entry that is u coming back
+                        tip = ut_better_covered(R, kc[w >> 1], ut_length(first, n_alive, n_unitigs, w >> 1), kc_u, len_u);
+                    }
+                }
+            }
+        }
+        flag[u] = tip ? 1 : 0;
+        const unsigned long long vote = __ballot(tip);
+        if (tip && (threadIdx.x & 63) == (uint32_t)__ffsll((long long)vote) - 1u) atomicAdd(&cnt->n_tips, (unsigned long long)__popcll(vote));
+    }
+}
+__global__ __launch_bounds__(256) void k_tip_mark(uint64_t n_slots, const uint64_t* __restrict__ loff, const uint64_t* __restrict__ links, const uint8_t* __restrict__ flag,
+                                                   uint32_t* __restrict__ work, TipCounters* __restrict__ cnt)
+{
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_slots; t += (uint64_t)gridDim.x * blockDim.x) {
+        if (flag[t >> 1]) continue;
+        bool any = false;
+        for (uint64_t p = loff[t], pe = loff[t + 1]; p < pe; p++) any = any || flag[links[p] >> 1];
+        if (!any) continue;
+        const uint32_t at = atomicAdd(&cnt->n_work[t & 1], 1u);      // (few: the neighbours of the round's tips; n_work[0] + n_work[1] <= n_slots < 2^32)
+        work[(t & 1) ? n_slots - 1 - at : at] = (uint32_t)t;
+    }
+}
+__global__ __launch_bounds__(256) void k_tip_kill(uint64_t n, const uint64_t* __restrict__ unitig, const uint8_t* __restrict__ flag, uint8_t* __restrict__ alive, uint8_t* __restrict__ masks,
+                                                   TipCounters* __restrict__ cnt)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t U = unitig[i];
+        const bool dies = U != ~0ull && flag[U >> 1];
+        if (dies) { alive[i] = 0; masks[i] = 0; }
+        const unsigned long long vote = __ballot(dies);
+        if (dies && (threadIdx.x & 63) == (uint32_t)__ffsll((long long)vote) - 1u) atomicAdd(&cnt->n_removed, (unsigned long long)__popcll(vote));
+    }
+}
+template <int KW>
+__global__ __launch_bounds__(GR_THREADS) void k_tip_refresh(QParams P, uint32_t n_ds, uint64_t n, const uint32_t* __restrict__ work, uint64_t n_work, const uint32_t* __restrict__ slot_rec,
+                                                             const uint8_t* __restrict__ alive, uint8_t* __restrict__ masks, TipCounters* __restrict__ cnt)
+{
+    typedef typename KeyT<KW>::type key_t;
+    constexpr int RB = 2 * (int)sizeof(key_t);
+    const uint32_t k = P.k, m = P.m;
+    const key_t kmask = KeyT<KW>::mask(k);
+    const uint32_t top = 2u * (k - 1);
+    for (uint64_t w = (uint64_t)blockIdx.x * GR_THREADS + threadIdx.x; w < n_work; w += (uint64_t)gridDim.x * GR_THREADS) {
+        const uint32_t sr = slot_rec[work[w]], s = sr & 1u;    // the record whose end s is this side; no other thread of this launch has the same record (one side per launch)
+        const uint64_t i = sr >> 1;
+        const uint32_t mk = masks[i], nib = (mk >> (4u * s)) & 15u;
+        if (!nib) continue;
+        const QDs D = P.ds[gr_dataset_of(P.ds, n_ds, i)];
+        const key_t x = q_load_key<key_t>(D.recs + (i - D.base) * (uint64_t)RB), rx = KeyT<KW>::revcomp(x, k);
+        uint32_t min_r, min_l;
+        gr_shared_minima<key_t>(P, x, min_r, min_l);
+        const uint32_t suf = (uint32_t)x & (P.mmask >> 2), pre = (uint32_t)(x >> (2u * (k - m + 1)));
+        uint32_t gone = 0;
+#pragma unroll
+        for (uint32_t h = 0; h < 2; h++) {                     // the four neighbours of the end, two searches in lock step at a time (k_unitig_link_fill)
+            bool act[2], found[2]; uint32_t d[2]; key_t key[2]; uint64_t at[2], base[2]; const uint8_t* recs[2];
+#pragma unroll
+            for (uint32_t q = 0; q < 2; q++) {
+                const uint32_t nt = 2u * h + q;
+                key_t fw, rv;
+                gr_neighbour<key_t>(P, x, rx, kmask, top, suf, pre, min_r, min_l, 4u * s + nt, fw, rv, d[q]);
+                key[q] = fw < rv ? fw : rv;
+                act[q] = (nib >> nt) & 1u;
+            }
+            q_search<key_t, RB, 2>(P, act, d, key, found, at, recs, base);
+#pragma unroll
+            for (uint32_t q = 0; q < 2; q++) {
+                if (!act[q]) continue;
+                const uint64_t j = base[q] + at[q];
+                if (found[q] && j < n) { if (!alive[j]) gone |= 1u << (2u * h + q); }
+                else cnt->bad = 1u;                            // the host answers GKC_ERR_ARG
+            }
+        }
+        if (gone) masks[i] = (uint8_t)(mk & ~(gone << (4u * s)));
+    }
+}
+
+extern "C" {
+
+int gkc_graph_tips_remove(gkc_ctx* c, uint8_t* d_masks, uint8_t* d_alive, const gkc_tip_params* params, uint64_t* n_rounds, uint64_t* tips_per_round, uint64_t* n_records_removed,
+                          uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles)
+{
+    static const char* who = "gkc_graph_tips_remove";
+    gkc_tun_refresh();
+    if (!c) return GKC_ERR_ARG;
+    if (n_rounds) *n_rounds = 0;
+    if (n_records_removed) *n_records_removed = 0;
+    if (n_unitigs) *n_unitigs = 0;
+    if (n_bases) *n_bases = 0;
+    if (n_cycles) *n_cycles = 0;
+    GKC_TRY(q_prepare(c, who));
+    UnitigPlacement& U = c->unitigs;
+    if (!params || params->rc_den == 0 || params->max_rounds > 64) { U.drop(); GKC_FAIL(c, GKC_ERR_ARG, "%s: the parameters are required, rc_den != 0, max_rounds <= 64", who); }
+    if (!d_masks || !d_alive) { U.drop(); GKC_FAIL(c, GKC_ERR_ARG, "%s: the masks (in, out) and the alive array (out) are required", who); }
+    if (tips_per_round) for (uint32_t r = 0; r < params->max_rounds; r++) tips_per_round[r] = 0;
+    const uint64_t n = gr_total(c);
+    const uint32_t n_ds = (uint32_t)c->datasets.size();
+    const TipRule R{c->k, params->max_len_topo, params->max_len_rc, params->rc_num, params->rc_den};
+    if (n) { GKC_HIP(c, hipMemsetAsync(d_alive, 1, (size_t)n, c->stream)); GKC_HIP(c, hipStreamSynchronize(c->stream)); }
+    uint64_t n_alive = n, removed = 0, rounds = 0;
+    bool placed = false;                                       // the placement in the context is that of d_masks / d_alive as they are now
+    for (uint32_t r = 0; r < params->max_rounds && !placed; r++) {
+        GKC_TRY(ut_build(c, who, d_masks, removed ? d_alive : nullptr, n_alive, nullptr, nullptr, nullptr));
+        const uint64_t nu = U.n_unitigs, n_slots = 2 * nu;
+        rounds++;
+        if (!nu) { placed = true; break; }                     // nothing alive: an empty round
+        uint64_t nl = 0;
+        int rc = ut_links(c, d_masks, nullptr, 0, nullptr, 0, &nl, nullptr);
+        DevBuf d_loff, d_lnk, d_slot, d_kc, d_flag, d_work, d_cnt;
+        if (rc == GKC_OK) rc = c->ensure(d_loff, (size_t)(n_slots + 1) * 8);
+        if (rc == GKC_OK) rc = c->ensure(d_lnk, (size_t)(nl ? nl : 1) * 8);
+        if (rc == GKC_OK) rc = c->ensure(d_slot, (size_t)n_slots * 4);
+        if (rc == GKC_OK) rc = c->ensure(d_kc, (size_t)nu * 8);
+        if (rc == GKC_OK) rc = c->ensure(d_flag, (size_t)nu);
+        if (rc == GKC_OK) rc = c->ensure(d_work, (size_t)n_slots * 4);
+        if (rc == GKC_OK) rc = c->ensure(d_cnt, sizeof(TipCounters));
+        if (rc == GKC_OK) rc = ut_links(c, d_masks, (uint64_t*)d_loff.p, nu, (uint64_t*)d_lnk.p, nl, &nl, (uint32_t*)d_slot.p);
+        if (rc != GKC_OK) { U.drop(); return rc; }
+        TipCounters h{};
+        hipError_t e;
+        {
+            ScopedTimer tm(c, "graph_tips");                   // its launch count: the rounds
+            const dim3 block(256), per_rec(q_grid((n + 255) / 256)), per_unitig(q_grid((nu + 255) / 256)), per_slot(q_grid((n_slots + 255) / 256));
+            const QDs* ds = (const QDs*)c->qidx.table.p;
+            const uint64_t* unitig = (const uint64_t*)U.unitig.p; const uint64_t* first = (const uint64_t*)U.first.p;
+            TipCounters* cnt = (TipCounters*)d_cnt.p;
+            e = hipMemsetAsync(d_kc.p, 0, (size_t)nu * 8, c->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, sizeof(TipCounters), c->stream);
+            if (e == hipSuccess) {
+                if (c->key_words == 1) hipLaunchKernelGGL((k_tip_kc<1>), per_rec, block, 0, c->stream, ds, n_ds, n, unitig, (unsigned long long*)d_kc.p);
+                else                   hipLaunchKernelGGL((k_tip_kc<2>), per_rec, block, 0, c->stream, ds, n_ds, n, unitig, (unsigned long long*)d_kc.p);
+                hipLaunchKernelGGL(k_tip_flags, per_unitig, block, 0, c->stream, R, nu, n_alive, first, (const uint64_t*)d_loff.p, (const uint64_t*)d_lnk.p, (const unsigned long long*)d_kc.p, (uint8_t*)d_flag.p, cnt);
+                hipLaunchKernelGGL(k_tip_mark, per_slot, block, 0, c->stream, n_slots, (const uint64_t*)d_loff.p, (const uint64_t*)d_lnk.p, (const uint8_t*)d_flag.p, (uint32_t*)d_work.p, cnt);
+                hipLaunchKernelGGL(k_tip_kill, per_rec, block, 0, c->stream, n, unitig, (const uint8_t*)d_flag.p, d_alive, d_masks, cnt);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(&h, cnt, sizeof(TipCounters), hipMemcpyDeviceToHost, c->stream);
+            hipError_t es = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = es;
+            if (e == hipSuccess && (uint64_t)h.n_work[0] + h.n_work[1] > n_slots) e = hipErrorUnknown;      // (cannot be: a slot is listed once)
+            if (e == hipSuccess && h.n_tips && (h.n_work[0] || h.n_work[1])) {
+                QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);
+                for (uint32_t side = 0; side < 2; side++) {    // one launch per side: a record is at most one slot of a side
+                    const uint64_t nw = h.n_work[side];
+                    if (!nw) continue;
+                    const uint32_t* work = (const uint32_t*)d_work.p + (side ? n_slots - nw : 0);
+                    const dim3 grid(q_grid((nw + GR_THREADS - 1) / GR_THREADS)), blk(GR_THREADS);
+                    if (c->key_words == 1) hipLaunchKernelGGL((k_tip_refresh<1>), grid, blk, 0, c->stream, P, n_ds, n, work, nw, (const uint32_t*)d_slot.p, (const uint8_t*)d_alive, d_masks, cnt);
+                    else                   hipLaunchKernelGGL((k_tip_refresh<2>), grid, blk, 0, c->stream, P, n_ds, n, work, nw, (const uint32_t*)d_slot.p, (const uint8_t*)d_alive, d_masks, cnt);
+                }
+                e = hipGetLastError();
+                if (e == hipSuccess) e = hipMemcpyAsync(&h.bad, &cnt->bad, 4, hipMemcpyDeviceToHost, c->stream);
+            }
+            es = hipStreamSynchronize(c->stream);              // (also after a failure: the scratch goes back to the pool)
+            if (e == hipSuccess) e = es;
+        }
+        if (e != hipSuccess) { U.drop(); GKC_HIP(c, e); }
+        if (tips_per_round) tips_per_round[r] = h.n_tips;
+        if (!h.n_tips) { placed = true; break; }
+        if (h.bad || h.n_removed > n_alive) { U.drop(); GKC_FAIL(c, GKC_ERR_ARG, "%s: d_masks name a neighbour that is no record of these results (the masks of other results?); d_masks and d_alive are not to be used", who); }
+        removed += h.n_removed; n_alive -= h.n_removed;
+    }
+    if (!placed) GKC_TRY(ut_build(c, who, d_masks, removed ? d_alive : nullptr, n_alive, nullptr, nullptr, nullptr));
+    if (n_rounds) *n_rounds = rounds;
+    if (n_records_removed) *n_records_removed = removed;
+    if (n_unitigs) *n_unitigs = U.n_unitigs;
+    if (n_bases) *n_bases = U.n_bases;
+    if (n_cycles) *n_cycles = U.n_cycles;
     return GKC_OK;
 }
 

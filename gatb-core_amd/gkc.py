@@ -34,6 +34,7 @@ SYMBOLS = [
     "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
     "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
+    "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -65,6 +66,11 @@ class PlanMsg(C.Structure):
 class CommStats(C.Structure):
     _fields_ = [("n_exchanges", C.c_uint64), ("bytes_sent", C.c_uint64), ("bytes_received", C.c_uint64), ("ms_transfer", C.c_double),
                 ("ms_host", C.c_double), ("reserved", C.c_uint64 * 4)]
+
+
+class TipParams(C.Structure):
+    """gkc_tip_params (include/gkc.h)"""
+    _fields_ = [(n, C.c_uint32) for n in ("max_len_topo", "max_len_rc", "rc_num", "rc_den", "max_rounds")]
 
 
 # gkc_read_abundance (include/gkc.h) as a numpy record
@@ -200,6 +206,8 @@ def lib():
         "gkc_graph_unitigs_write": (C.c_int, [vp, vp, u64, vp, u64, vp]),
         "gkc_graph_unitigs_nodes": (C.c_int, [vp, vp, vp]),
         "gkc_graph_unitigs_links": (C.c_int, [vp, vp, vp, u64, vp, u64, P(u64)]),
+        "gkc_graph_unitigs_build_alive": (C.c_int, [vp, vp, vp, P(u64), P(u64), P(u64)]),
+        "gkc_graph_tips_remove": (C.c_int, [vp, vp, vp, P(TipParams), P(u64), vp, P(u64), P(u64), P(u64), P(u64)]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -345,6 +353,7 @@ class Counter:
         self._chk(self.L.gkc_set_batch_keys(self.h, max_keys))
 
     def begin_pass(self, p=0):
+        self._tips = None                                       # the masks and the alive array of remove_tips go with the results they describe
         self._chk(self.L.gkc_begin_pass(self.h, p))
 
     def push_reads(self, bases, offsets):
@@ -723,7 +732,8 @@ class Counter:
         return b.cpu().numpy(), o.cpu().numpy().view(np.uint64), kc.cpu().numpy().view(np.uint64)
 
     def unitig_of_records(self):
-        """per solid record, dataset order, from the placement of the last unitigs_build / unitigs -> (unitig index uint64[n], reversed bool[n], pos uint32[n])"""
+        """per solid record, dataset order, from the placement of the last unitigs_build / unitigs / remove_tips -> (unitig index uint64[n], reversed bool[n],
+        pos uint32[n]); a dead record of the placement remove_tips left: unitig 2^64 - 1, not reversed, pos 0"""
         import torch
         n = C.c_uint64()
         self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
@@ -731,7 +741,8 @@ class Counter:
         torch.cuda.synchronize()
         self._chk(self.L.gkc_graph_unitigs_nodes(self.h, u.data_ptr(), p.data_ptr()))
         u = u[: n.value].cpu().numpy().view(np.uint64)
-        return u >> np.uint64(1), (u & np.uint64(1)).astype(bool), p[: n.value].cpu().numpy().view(np.uint32)
+        dead = u == np.uint64(M64)
+        return np.where(dead, np.uint64(M64), u >> np.uint64(1)), ((u & np.uint64(1)) != 0) & ~dead, p[: n.value].cpu().numpy().view(np.uint32)
 
     # ---- links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
     def unitig_links_device(self, d_masks=None):
@@ -765,18 +776,73 @@ class Counter:
         self._chk(self.L.gkc_graph_unitigs_links(self.h, d_masks, offsets.data_ptr(), nu, links.data_ptr(), nl.value, C.byref(nl)))
         return offsets, links[: nl.value]
 
+    # ---- tips (include/gkc.h, "tips")
+    def remove_tips(self, max_len_topo=None, max_len_rc=None, rc_ratio=(2, 1), max_rounds=20):
+        """removes the tips of the compacted graph round by round (gkc_graph_tips_remove) and leaves the simplified graph as the context's placement. Defaults: the
+        reference's constants, max_len_topo = 5 k // 2 bases, max_len_rc = 10 k bases, ratio 2 / 1; 0 switches a rule off. -> dict: alive bool[n_solid], rounds,
+        tips_per_round (list), records_removed, n_unitigs, n_bases, n_cycles. The device masks and alive array stay on the object until the next count
+        (simplified_unitigs, write_unitigs_fasta(simplified=True) read them)."""
+        import torch
+        k = self.k
+        prm = TipParams((5 * k) // 2 if max_len_topo is None else max_len_topo, 10 * k if max_len_rc is None else max_len_rc, rc_ratio[0], rc_ratio[1], max_rounds)
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+        masks = torch.zeros(max(n.value, 16), dtype=torch.uint8, device="cuda"); alive = torch.zeros(max(n.value, 16), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        if n.value:
+            self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
+        per_round = np.zeros(max(1, min(max_rounds, 64)), np.uint64)
+        nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
+        self._tips = None
+        self._chk(self.L.gkc_graph_tips_remove(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), C.byref(nr), _p(per_round), C.byref(rem), C.byref(nu), C.byref(nb), C.byref(nc)))
+        self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
+        return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, tips_per_round=[int(x) for x in per_round[: nr.value]], records_removed=rem.value,
+                    n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value)
+
+    def simplified_masks(self):
+        """-> uint8[n_solid]: the neighbour masks of the graph remove_tips left (0 for dead records)"""
+        t = self._tips_state()
+        return t["masks"][: t["n"]].cpu().numpy()
+
+    def _tips_state(self):
+        t = getattr(self, "_tips", None)
+        if t is None:
+            raise GkcError("remove_tips must be called first (after the last count)")
+        return t
+
+    def simplified_unitigs(self):
+        """the graph remove_tips left -> (bases uint8[n_bases], offsets uint64[n_unitigs + 1], kc uint64[n_unitigs], link_offsets uint64[2 n_unitigs + 1],
+        links uint64[n_links]) as numpy, in the layouts of unitigs() and unitig_links(). The placement in the context must still be the one remove_tips left
+        (unitigs_build and the methods over it replace it: call remove_tips again)."""
+        import torch
+        t = self._tips_state()
+        nu, nb = t["n_unitigs"], t["n_bases"]
+        bases = torch.zeros(max(nb, 16), dtype=torch.uint8, device="cuda")
+        offsets = torch.zeros(nu + 1, dtype=torch.int64, device="cuda"); kc = torch.zeros(max(nu, 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        self._chk(self.L.gkc_graph_unitigs_write(self.h, bases.data_ptr(), nb, offsets.data_ptr(), nu, kc.data_ptr()))
+        lo, links = self._unitig_links_of_placement(nu, t["masks"].data_ptr())
+        if int(offsets[-1]) != nb:
+            raise GkcError("the placement in the context is not the one remove_tips left (call remove_tips again)")
+        return (bases[:nb].cpu().numpy(), offsets.cpu().numpy().view(np.uint64), kc[:nu].cpu().numpy().view(np.uint64), lo.cpu().numpy().view(np.uint64),
+                links.cpu().numpy().view(np.uint64))
+
     def unitig_links(self, d_masks=None):
         """-> (link_offsets uint64[2 n_unitigs + 1], links uint64[n_links]) as numpy, see unitig_links_device"""
         o, l = self.unitig_links_device(d_masks)
         return o.cpu().numpy().view(np.uint64), l.cpu().numpy().view(np.uint64)
 
-    def write_unitigs_fasta(self, path, d_masks=None):
+    def write_unitigs_fasta(self, path, d_masks=None, simplified=False):
         """the unitigs with their links in the layout of bcalm2 that the reference's GraphUnitigs::load_unitigs parses: per unitig
         ">u LN:i:<bases> KC:i:<kc> km:f:<kc / records, one decimal>  L:+:v:+- ... L:-:v:+- ..." (the '+' side's links first, each side in slot order), the sequence on
-        the next line. Host code over unitigs() and unitig_links() -> (n_unitigs, n_links)"""
-        keep, d_masks = self._masks_once(d_masks)
-        bases, offs, kc = self.unitigs(d_masks)
-        lo, links = (t.cpu().numpy().view(np.uint64) for t in self._unitig_links_of_placement(len(kc), d_masks))
+        the next line. Host code over unitigs() and unitig_links(), or, with ``simplified``, over simplified_unitigs(): the graph remove_tips left
+        -> (n_unitigs, n_links)"""
+        if simplified:
+            bases, offs, kc, lo, links = self.simplified_unitigs()
+        else:
+            keep, d_masks = self._masks_once(d_masks)
+            bases, offs, kc = self.unitigs(d_masks)
+            lo, links = (t.cpu().numpy().view(np.uint64) for t in self._unitig_links_of_placement(len(kc), d_masks))
         k = self.k
         text = bases.tobytes().decode()
         with open(path, "w") as f:

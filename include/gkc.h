@@ -189,7 +189,7 @@ int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
  * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
  * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers"; of the graph neighbourhoods: "graph_neighbors",
- * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit", "graph_unitig_links" */
+ * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit", "graph_unitig_links"; of the tip removal: "graph_tips" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -510,6 +510,43 @@ int gkc_graph_unitigs_nodes(gkc_ctx* ctx, uint64_t* d_unitig, uint32_t* d_pos);
  * No solid k-mer: GKC_OK, offsets[0] = 0, *n_links = 0. */
 int gkc_graph_unitigs_links(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* d_link_offsets, uint64_t cap_unitigs,
                             uint64_t* d_links, uint64_t cap_links, uint64_t* n_links);
+
+/* ---- tips: dead-end branches of the compacted graph removed round by round, on the device ----------------------------------------------------------
+ * The first step of the reference's Simplifications::simplify() (removeTips), on the unitigs and links above. All terms are those of the unitigs and their links.
+ *   alive  : one byte per solid record, flat order; every record starts alive. A dead record is a record of no unitig: its mask is 0 and no alive record's mask names
+ *            it. The unitigs of an alive set are the unitigs above over the alive records only, numbered by ascending start record among them.
+ *   round  : starts from the masks and alive as they are; takes the unitigs and links of the alive subgraph. Unitig u has L_u records, bases(u) = L_u + k - 1, abundance
+ *            sum KC_u. u is a CANDIDATE when exactly one of its two slots has no link and the other, t = 2u + su, has at least one (a slot that links to u's own other
+ *            slot counts as linked; no special case for hairpins, self-links or palindromes; an isolated unitig or an isolated cycle never is a candidate).
+ *   tip    : a candidate with bases(u) <= max_len_topo (the topological rule), or with bases(u) <= max_len_rc and some competitor c such that
+ *            KC_c * L_u * rc_den > rc_num * KC_u * L_c (strict, in exact integers, no floating point). The competitors of u, per entry (v, m) of slot t: the unitig v
+ *            itself and every entry (w, .) of v's arrival slot 2v + (1 - m) except the ONE entry (u, 1 - su) that is u coming back.
+ *            All tips of a round are decided on the graph at its start and removed together: every record of a tip dies and its mask becomes 0, and every bit of an alive
+ *            record's mask that named a dead record is cleared. The next round compacts again: two unitigs a tip kept apart become one.
+ * Rounds run until one removes nothing or max_rounds have run.
+ * Against the reference: the topological rule is its removeTips pass on a freshly compacted graph, for odd k (k + simplePathLength from a dead-end extremity is the
+ * unitig's length in bases, the deletions are deferred to the end of the pass, later passes walk simple paths across joined unitigs). The coverage rule is NOT the
+ * reference's (which averages floating-point means of means of the neighbours): it is "some competitor is that much better covered" in integers, and no parity is
+ * claimed for it. The stop rule is this library's (the reference's depends on its cutoff events, 20 passes at most). Bulges, erroneous connections and the removal of
+ * isolated short unitigs are not served.
+ * Timing name of gkc_get_timing: "graph_tips" (flags, kill, refresh of every round; its launch count: the rounds). The builds and links inside the rounds go to the
+ * names of the unitigs. */
+typedef struct gkc_tip_params {
+    uint32_t max_len_topo, max_len_rc;     /* lengths in bases; 0 switches the rule off */
+    uint32_t rc_num, rc_den;               /* the ratio of the coverage rule; rc_den == 0: GKC_ERR_ARG */
+    uint32_t max_rounds;                   /* 0 does nothing (the placement is the plain build's); more than 64: GKC_ERR_ARG */
+} gkc_tip_params;
+/* gkc_graph_unitigs_build over the alive records only. d_alive: u8[n_solid]. d_masks: required, and already consistent with d_alive (a dead record has mask 0 and
+ * nothing names it). Afterwards gkc_graph_unitigs_nodes reports ~0 / pos 0 for dead records, gkc_graph_unitigs_write emits only alive records
+ * (n_bases = n_alive + n_unitigs (k - 1)), gkc_graph_unitigs_links with the same masks gives the links of the subgraph, and with d_masks == NULL GKC_ERR_ARG (the
+ * library cannot recompute edited masks). All records dead, or no records: GKC_OK, 0 unitigs, gkc_graph_unitigs_write gives offsets[0] = 0. */
+int gkc_graph_unitigs_build_alive(gkc_ctx* ctx, const uint8_t* d_masks, const uint8_t* d_alive, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
+/* d_masks (in, out): on entry what gkc_graph_neighbors_solid wrote for these results; NULL is GKC_ERR_ARG (the edited masks are part of the result). d_alive (out):
+ * n_solid bytes. On return they describe the final subgraph and the placement in the context is that of gkc_graph_unitigs_build_alive on them (of the plain build when
+ * nothing was removed). *n_rounds: the rounds run, the last, empty one included. tips_per_round: host u64[max_rounds] or NULL. State rules, error behaviour and the
+ * invalidation by a recount are those of gkc_graph_unitigs_build; masks that name a neighbour which is no record: GKC_ERR_ARG, d_masks / d_alive then hold no result. */
+int gkc_graph_tips_remove(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const gkc_tip_params* params, uint64_t* n_rounds, uint64_t* tips_per_round,
+                          uint64_t* n_records_removed, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

@@ -34,7 +34,7 @@ SYMBOLS = [
     "gkc_query_reads_device", "gkc_query_reads", "gkc_query_kmers_device", "gkc_query_kmers", "gkc_query_read_summary_device", "gkc_query_banks_reads_device",
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
     "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
-    "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove",
+    "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove", "gkc_graph_simplify",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -71,6 +71,21 @@ class CommStats(C.Structure):
 class TipParams(C.Structure):
     """gkc_tip_params (include/gkc.h)"""
     _fields_ = [(n, C.c_uint32) for n in ("max_len_topo", "max_len_rc", "rc_num", "rc_den", "max_rounds")]
+
+
+class SimplifyParams(C.Structure):
+    """gkc_simplify_params (include/gkc.h)"""
+    _fields_ = [("tips", TipParams)] + [(n, C.c_uint32) for n in (
+        "bulge_max_len", "bulge_alt_num", "bulge_alt_den", "bulge_alt_add", "bulge_max_rounds", "ec_max_len", "ec_num", "ec_den", "ec_max_rounds", "max_sweeps", "resume")]
+
+
+class SimplifyRound(C.Structure):
+    """gkc_simplify_round (include/gkc.h)"""
+    _fields_ = [("kind", C.c_uint32), ("sweep", C.c_uint32), ("n_unitigs", C.c_uint64), ("n_hits", C.c_uint64), ("n_records_removed", C.c_uint64)]
+
+
+SIMPLIFY_KINDS = ("tips", "bulges", "ec")
+SIMPLIFY_LOG_CAP = 64 + 16 * 3 * 64                             # the most rounds a call can run
 
 
 # gkc_read_abundance (include/gkc.h) as a numpy record
@@ -208,6 +223,7 @@ def lib():
         "gkc_graph_unitigs_links": (C.c_int, [vp, vp, vp, u64, vp, u64, P(u64)]),
         "gkc_graph_unitigs_build_alive": (C.c_int, [vp, vp, vp, P(u64), P(u64), P(u64)]),
         "gkc_graph_tips_remove": (C.c_int, [vp, vp, vp, P(TipParams), P(u64), vp, P(u64), P(u64), P(u64), P(u64)]),
+        "gkc_graph_simplify": (C.c_int, [vp, vp, vp, P(SimplifyParams), P(SimplifyRound), u64, P(u64), P(u64), P(u64), P(u64), P(u64)]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -799,15 +815,60 @@ class Counter:
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, tips_per_round=[int(x) for x in per_round[: nr.value]], records_removed=rem.value,
                     n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value)
 
+    # ---- simplify (include/gkc.h, "simplify")
+    def simplify_params(self, max_len_topo=None, max_len_rc=None, rc_ratio=(2, 1), tip_rounds=20, bulge_max_len=None, bulge_alt=(11, 10, 3), bulge_rounds=20,
+                        ec_max_len=None, ec_ratio=(4, 1), ec_rounds=20, max_sweeps=10, resume=False):
+        """-> SimplifyParams with the reference's constants where an argument is None: tips as remove_tips, bulge_max_len = max(3 k, k + 100) bases, alternative up to
+        max(11 / 10 L, L + 3) records, ec_max_len = 9 k bases, ratio 4 / 1; 20 rounds per phase, 10 sweeps"""
+        k = self.k
+        tips = TipParams((5 * k) // 2 if max_len_topo is None else max_len_topo, 10 * k if max_len_rc is None else max_len_rc, rc_ratio[0], rc_ratio[1], tip_rounds)
+        return SimplifyParams(tips, max(3 * k, k + 100) if bulge_max_len is None else bulge_max_len, bulge_alt[0], bulge_alt[1], bulge_alt[2], bulge_rounds,
+                              9 * k if ec_max_len is None else ec_max_len, ec_ratio[0], ec_ratio[1], ec_rounds, max_sweeps, 1 if resume else 0)
+
+    def simplify(self, params=None, **kw):
+        """tips, bulges and erroneous connections of the compacted graph removed on the device (gkc_graph_simplify): phase(tips), then sweeps of phase(bulges),
+        phase(ec), phase(tips) until a sweep removes nothing, and the simplified graph left as the context's placement. ``params``: a SimplifyParams, or the keyword
+        arguments of simplify_params. With resume the state an earlier remove_tips / simplify left on this object is continued, otherwise every record starts alive.
+        -> dict: alive bool[n_solid], rounds, records_removed (of this call), n_unitigs, n_bases, n_cycles, log: a list of (kind name, sweep, n_unitigs, n_hits,
+        n_records_removed) per round. The device masks and alive array stay on the object until the next count, as after remove_tips."""
+        import torch
+        prm = params if params is not None else self.simplify_params(**kw)
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_neighbors_solid(self.h, None, C.byref(n)))
+        if prm.resume:
+            t = self._tips_state()
+            masks, alive = t["masks"], t["alive"]
+        else:
+            masks = torch.zeros(max(n.value, 16), dtype=torch.uint8, device="cuda"); alive = torch.zeros(max(n.value, 16), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            if n.value:
+                self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
+        log = (SimplifyRound * SIMPLIFY_LOG_CAP)()
+        nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
+        self._tips = None
+        self._chk(self.L.gkc_graph_simplify(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), log, SIMPLIFY_LOG_CAP, C.byref(nr), C.byref(rem), C.byref(nu), C.byref(nb),
+                                            C.byref(nc)))
+        self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
+        return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, records_removed=rem.value, n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value,
+                    log=[(SIMPLIFY_KINDS[e.kind], int(e.sweep), int(e.n_unitigs), int(e.n_hits), int(e.n_records_removed)) for e in log[: min(nr.value, SIMPLIFY_LOG_CAP)]])
+
+    def remove_bulges(self, bulge_max_len=None, bulge_alt=(11, 10, 3), max_rounds=20, resume=False):
+        """the bulges alone: simplify with no tip and no EC rounds, i.e. one phase(bulges) and the empty sweep after it"""
+        return self.simplify(tip_rounds=0, ec_rounds=0, bulge_max_len=bulge_max_len, bulge_alt=bulge_alt, bulge_rounds=max_rounds, resume=resume)
+
+    def remove_erroneous_connections(self, ec_max_len=None, ec_ratio=(4, 1), max_rounds=20, resume=False):
+        """the erroneous connections alone: simplify with no tip and no bulge rounds"""
+        return self.simplify(tip_rounds=0, bulge_rounds=0, ec_max_len=ec_max_len, ec_ratio=ec_ratio, ec_rounds=max_rounds, resume=resume)
+
     def simplified_masks(self):
-        """-> uint8[n_solid]: the neighbour masks of the graph remove_tips left (0 for dead records)"""
+        """-> uint8[n_solid]: the neighbour masks of the graph remove_tips / simplify left (0 for dead records)"""
         t = self._tips_state()
         return t["masks"][: t["n"]].cpu().numpy()
 
     def _tips_state(self):
         t = getattr(self, "_tips", None)
         if t is None:
-            raise GkcError("remove_tips must be called first (after the last count)")
+            raise GkcError("remove_tips or simplify must be called first (after the last count)")
         return t
 
     def simplified_unitigs(self):

@@ -189,7 +189,8 @@ int gkc_get_stats(gkc_ctx* ctx, gkc_stats* out);
 /* Kernel timing of the last gkc_finish_pass / pushes (HIP events on the context's stream), milliseconds.
  * names: "scan_count", "scan_emit", "expand_count", "expand_scatter", "bucket_sort", "compact", "total_stage_a", "total_stage_b";
  * of the abundance queries (accumulated since gkc_configure): "query_index", "query_reads", "query_kmers"; of the graph neighbourhoods: "graph_neighbors",
- * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit", "graph_unitig_links"; of the tip removal: "graph_tips" */
+ * "graph_branching"; of the unitigs: "graph_links", "graph_rank", "graph_emit", "graph_unitig_links"; of the tip removal: "graph_tips";
+ * of the bulges and erroneous connections: "graph_bulges", "graph_ec" */
 int gkc_get_timing(gkc_ctx* ctx, const char* name, double* ms, uint64_t* launches);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -527,8 +528,8 @@ int gkc_graph_unitigs_links(gkc_ctx* ctx, const uint8_t* d_masks, uint64_t* d_li
  * Against the reference: the topological rule is its removeTips pass on a freshly compacted graph, for odd k (k + simplePathLength from a dead-end extremity is the
  * unitig's length in bases, the deletions are deferred to the end of the pass, later passes walk simple paths across joined unitigs). The coverage rule is NOT the
  * reference's (which averages floating-point means of means of the neighbours): it is "some competitor is that much better covered" in integers, and no parity is
- * claimed for it. The stop rule is this library's (the reference's depends on its cutoff events, 20 passes at most). Bulges, erroneous connections and the removal of
- * isolated short unitigs are not served.
+ * claimed for it. The stop rule is this library's (the reference's depends on its cutoff events, 20 passes at most). Bulges and erroneous connections are served by
+ * gkc_graph_simplify (section "simplify" below); the removal of isolated short unitigs is not served.
  * Timing name of gkc_get_timing: "graph_tips" (flags, kill, refresh of every round; its launch count: the rounds). The builds and links inside the rounds go to the
  * names of the unitigs. */
 typedef struct gkc_tip_params {
@@ -547,6 +548,53 @@ int gkc_graph_unitigs_build_alive(gkc_ctx* ctx, const uint8_t* d_masks, const ui
  * invalidation by a recount are those of gkc_graph_unitigs_build; masks that name a neighbour which is no record: GKC_ERR_ARG, d_masks / d_alive then hold no result. */
 int gkc_graph_tips_remove(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const gkc_tip_params* params, uint64_t* n_rounds, uint64_t* tips_per_round,
                           uint64_t* n_records_removed, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
+
+/* ---- simplify: tips, bulges and erroneous connections of the compacted graph, on the device ---------------------------------------------------------
+ * The three steps of the reference's Simplifications::simplify() (removeTips, removeBulges, removeErroneousConnections) in its order. All terms are those of "unitigs",
+ * their links and "tips": slot t = 2u + side, L_u records, bases(u) = L_u + k - 1, abundance sum KC_u.
+ *   names  : slot (u, s) NAMES slot (v, 1 - m) when (v, m) is an entry of slot 2u + s: the arrival slot of the tips text. At odd k naming is symmetric; at even k these
+ *            sentences are the whole definition and no parity is claimed.
+ *   round  : of one kind (0 tips, 1 bulges, 2 erroneous connections), decided on the graph at its start; all hits are removed together exactly as a tip round does it:
+ *            the records of a hit die, their masks become 0, every bit of an alive record's mask that named a dead record is cleared, the next round compacts again.
+ *   bulge  : (a simple bubble) unitig u is a bulge when all of the following hold.
+ *            1. Both of its slots have at least one entry, and bases(u) <= bulge_max_len.
+ *            2. There is a unitig c != u, taken in an orientation o in {0, 1}, that runs parallel to it: there is a slot X whose unitig is neither u nor c such that
+ *               (u, 0) names X, X names (c, o) and (c, o) names X; and a slot Y whose unitig is neither u nor c such that (u, 1) names Y and (c, 1 - o) names Y.
+ *            3. L_c <= max(L_u * bulge_alt_num / bulge_alt_den, L_u + bulge_alt_add), in integer division (the reference's maxlen: 11 / 10 and + 3).
+ *            4. c beats u: KC_u * L_c < KC_c * L_u, or the two products are equal and c < u (exact integers). "Beats" is a strict total order: of any set of mutually
+ *               parallel unitigs the best covered one is never removed, and two twins never remove each other.
+ *            The work per unitig is bounded: at most 4 X of at most 4 entries each give at most 16 (c, o), each checked against at most 4 x 4 slot pairs.
+ *   EC     : (erroneous connection) unitig u is an EC when all of the following hold.
+ *            1. Both slots have at least one entry, and bases(u) <= ec_max_len.
+ *            2. On each of its two sides some slot it names has at least two entries: u has a sibling at both ends (the Z shape of the reference's comment).
+ *            3. On at least one side some competitor c != u has KC_c * L_u * ec_den > ec_num * KC_u * L_c (strict, exact integers). The competitors of a side are those
+ *               of the tips rule: per entry (v, m) of the slot, v itself and every entry of v's arrival slot except the ONE entry that is u coming back.
+ *            A single-record unitig can be an EC.
+ *   phase  : phase(kind) runs rounds of that kind until one removes nothing or the kind's max_rounds have run; a kind whose max_rounds is 0 is skipped.
+ *   call   : phase(tips) (sweep 0), then sweeps 1, 2, ... of phase(bulges), phase(ec), phase(tips), until a whole sweep removes nothing or max_sweeps have run.
+ * Against the reference: the order is that of its simplify() (tips to exhaustion, then bulges and ECs, then a mix); the stop rule is this library's. The bulge rule
+ * differs: the reference accepts cov_u <= 1.1 cov_alt and searches alternative paths of several unitigs (heuristic_most_covered_path); here the alternative is ONE unitig
+ * and the comparison is strict. The EC rule is in integers; the reference skips pathLen == 0, this library removes nodes of any path length. What is claimed: the
+ * reference's three unit tests with known answers (debruijn_simplunitigs_bubble, _bubble_snp, _ec; tests/golden/reference_simplify_vectors.json), nothing more.
+ * Not served: alternative paths of several unitigs, the reference's floating-point coverage rules, the removal of isolated short unitigs, the drop-in, communicators,
+ * the merged state of a gkc_banks.
+ * Timing names of gkc_get_timing: "graph_bulges" and "graph_ec" (KC when the round is the first on its graph, flags, mark, kill and refresh of that kind's rounds; launch
+ * count: that kind's rounds on a graph that has unitigs); tip rounds inside keep "graph_tips". A round that removed nothing leaves placement, link CSR and KC valid and
+ * the next round starts on them: a call runs (rounds that removed something) + 1 builds, observable as the launch count of "graph_links". */
+typedef struct gkc_simplify_params {
+    gkc_tip_params tips;                   /* tips.max_rounds: per phase; 0 = no tip phases */
+    uint32_t bulge_max_len, bulge_alt_num, bulge_alt_den, bulge_alt_add, bulge_max_rounds;
+    uint32_t ec_max_len, ec_num, ec_den, ec_max_rounds;
+    uint32_t max_sweeps;                   /* 0: only the leading tip phase; > 16: GKC_ERR_ARG */
+    uint32_t resume;                       /* 0: every record starts alive (d_alive is written first); 1: d_masks / d_alive are a consistent state an earlier call left */
+} gkc_simplify_params;
+typedef struct gkc_simplify_round { uint32_t kind /* 0 tips, 1 bulges, 2 ec */, sweep; uint64_t n_unitigs, n_hits, n_records_removed; } gkc_simplify_round;
+/* d_masks, d_alive, the counts on return, state rules, error behaviour and invalidation: those of gkc_graph_tips_remove; the context's placement is the final graph's and
+ * gkc_graph_unitigs_write / _nodes / _links answer for it. *n_rounds: every round run, empty ones included; log: host, receives the first cap_log of them (n_unitigs: of
+ * the graph the round was decided on), or NULL. Any zero denominator, a max_rounds above 64 or max_sweeps above 16: GKC_ERR_ARG. resume = 1: d_alive is read, a dead
+ * record with a mask and masks that name a dead or missing record are GKC_ERR_ARG. No solid k-mer: GKC_OK, zero counts. */
+int gkc_graph_simplify(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const gkc_simplify_params* params, gkc_simplify_round* log, uint64_t cap_log,
+                       uint64_t* n_rounds, uint64_t* n_records_removed, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

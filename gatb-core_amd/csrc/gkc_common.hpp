@@ -425,10 +425,12 @@ int gkc_export_superkmers(gkc_ctx* c, uint32_t part, uint8_t* out, uint64_t cap,
 int gkc_require_resident(gkc_ctx* c, const char* who);
 int gkc_launch_mark_read_starts(gkc_ctx* c, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t* d_bits, uint32_t* d_bad);      // gkc_scan.hip
 // gkc_query.hip: (re)builds ix over `ds` at the current GKC_QUERY_INDEX_STRIDE (bare: 8 / 16-byte keys, else Count records); the reads kernel against it — planes != nullptr: the
-// merged state of a gkc_banks, d_out = sum over the nb_banks planes and d_vectors (may be NULL) the rows
+// merged state of a gkc_banks, d_out = sum over the nb_banks planes and d_vectors (may be NULL) the rows; nodes != nullptr (gkc_paths.hip, the context's own results only):
+// the placement of every k-mer instead of its abundance, d_out unused, timed as "graph_read_nodes"
+struct QNodes;
 int gkc_query_index_build(gkc_ctx* c, QueryIndex& ix, const std::vector<QHostDs>& ds, uint32_t key_words, bool bare);
 int gkc_query_reads_run(gkc_ctx* c, const QueryModel& M, const QueryIndex& ix, const int32_t* const* planes, uint32_t nb_banks, const char* d_bases, const uint64_t* d_offsets,
-                        uint64_t n_reads, uint64_t n_bases, int32_t* d_out, int32_t* d_vectors, const char* who);
+                        uint64_t n_reads, uint64_t n_bases, int32_t* d_out, int32_t* d_vectors, const char* who, const QNodes* nodes = nullptr);
 // packed result batches (gkc_sink.hip). tun: the tunables the call works with — a Stage-B lane hands in its pass's snapshot, everyone else gkc_tun()
 bool  gkc_sink_packed(gkc_ctx* c, const GkcTun& tun);
 bool  gkc_sink_host_behind(gkc_ctx* c, uint64_t n_records, const GkcTun& tun);   // several ranks on one host: landed, unexpanded records beyond 1.5 batches -> this batch travels raw

@@ -84,3 +84,6 @@ __device__ __forceinline__ uint32_t gr_load4_masks(const uint8_t* __restrict__ f
 uint64_t gr_total(const gkc_ctx* c);                          // solid records of all datasets
 // masks of the records [g0, g0 + n) of the flat order into d_masks[0, n); q_prepare has run
 int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks);
+// ------------------------------------------------------------------------------------------------ host side (gkc_unitigs.hip)
+// q_prepare, then: the context holds a placement and it describes the results the context holds now (GKC_ERR_ARG otherwise)
+int ut_require_placement(gkc_ctx* c, const char* who);

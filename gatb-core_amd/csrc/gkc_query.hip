@@ -9,6 +9,8 @@
 //                order: one gather from d_mkey_lut), the window minimum by the shared-core + prefix / suffix scheme of Stage A, validity from the read-start and invalid
 //                bit planes. Unlike Stage A the k-mer integer IS formed here (from the big-endian plane), canonicalised in registers.
 //   k_q_kmers  : one thread per key; the m-mers come out of the key by shifts; the same routing and search.
+//                The kernel has three modes (QM_COUNTS, QM_BANKS, QM_NODES of gkc_query.hpp): everything up to the search is shared, the answer step differs. QM_NODES
+//                (gkc_graph_reads_nodes_device, gkc_paths.hip) gathers the placement of the record found and stores 8 x 16 B of nodes and 4 x 16 B of positions.
 //   search     : a sampled index — the key of every S-th record of every dataset in one compact array (QueryIndex, S = GKC_QUERY_INDEX_STRIDE, default 256) — is searched
 //                first (small enough to stay in the Infinity Cache), the remaining <= log2(S) steps stay inside one window of S records. A thread runs the searches of two
 //                positions in lock step so that two independent loads are in flight per lane.
@@ -45,10 +47,11 @@ __device__ __forceinline__ int32_t q_answer(const QParams& P, const QPlanes& PL,
 }
 
 // ------------------------------------------------------------------------------------------------ reads
-template <int KW, bool BANKS>
-__global__ __launch_bounds__(QR_THREADS) void k_q_reads(QParams P, QPlanes PL)
+template <int KW, int MODE>
+__global__ __launch_bounds__(QR_THREADS) void k_q_reads(QParams P, typename QExtra<MODE>::type PL)
 {
     typedef typename KeyT<KW>::type key_t;
+    constexpr bool BANKS = MODE == QM_BANKS, NODES = MODE == QM_NODES;
     constexpr int RB = BANKS ? (int)sizeof(key_t) : 2 * (int)sizeof(key_t);
     __shared__ uint32_t s_be[QR_WORDS + QR_PAD];
     __shared__ uint32_t s_le[QR_WORDS + QR_PAD];
@@ -165,12 +168,14 @@ __global__ __launch_bounds__(QR_THREADS) void k_q_reads(QParams P, QPlanes PL)
         }
 
         // ---- canonical k-mer, dataset, search: QR_LOCKSTEP positions at a time ----
-        int32_t res[16];
+        int32_t res[NODES ? 1 : 16];
+        uint64_t node[NODES ? 16 : 1]; uint32_t npos[NODES ? 16 : 1];      // QM_NODES: unitig << 1 | strand or a GKC_NODE_* sentinel, and the position in the unitig
         const uint64_t g0 = t0 + (uint64_t)p0;
 #pragma unroll
         for (int j0 = 0; j0 < 16; j0 += QR_LOCKSTEP) {
             bool act[QR_LOCKSTEP], found[QR_LOCKSTEP]; uint32_t d[QR_LOCKSTEP]; key_t key[QR_LOCKSTEP]; uint64_t pos[QR_LOCKSTEP], base[QR_LOCKSTEP];
             const uint8_t* recs[QR_LOCKSTEP];
+            bool flip[QR_LOCKSTEP];                            // QM_NODES: the read spells the reverse complement of the record
 #pragma unroll
             for (int u = 0; u < QR_LOCKSTEP; u++) {
                 const int j = j0 + u;
@@ -188,18 +193,40 @@ __global__ __launch_bounds__(QR_THREADS) void k_q_reads(QParams P, QPlanes PL)
                 }
                 const key_t rv = KeyT<KW>::revcomp(fw, k);
                 key[u] = fw < rv ? fw : rv;                    // Model.hpp:294
+                if constexpr (NODES) flip[u] = rv < fw;        // (a palindrome stands forward)
                 d[u] = q_dataset_of(P, mz[j]);
             }
             q_search<key_t, RB, QR_LOCKSTEP>(P, act, d, key, found, pos, recs, base);
 #pragma unroll
             for (int u = 0; u < QR_LOCKSTEP; u++) {
                 const uint64_t g = g0 + (uint64_t)(j0 + u);
-                if (BANKS) { if (g < P.n_bases) { const int32_t s = q_answer<key_t, true>(P, PL, act[u] && found[u], recs[u], pos[u], base[u], g); res[j0 + u] = act[u] ? s : -1; } else res[j0 + u] = -1; }
+                if constexpr (NODES) {
+                    // the record's placement (unitig << 1 | reversed, ~0: a record of no unitig) with the strand the read spells it on
+                    const bool hit = act[u] && found[u];
+                    const uint64_t i = base[u] + pos[u], U = hit ? PL.unitig[i] : ~0ull;
+                    const bool placed = hit && U != ~0ull;
+                    node[j0 + u] = !act[u] ? GKC_NODE_NO_KMER : (!found[u] ? GKC_NODE_ABSENT : (placed ? (U ^ (flip[u] ? 1ull : 0ull)) : GKC_NODE_REMOVED));
+                    npos[j0 + u] = (placed && PL.out_pos) ? PL.pos[i] : 0u;
+                } else if (BANKS) { if (g < P.n_bases) { const int32_t s = q_answer<key_t, true>(P, PL, act[u] && found[u], recs[u], pos[u], base[u], g); res[j0 + u] = act[u] ? s : -1; } else res[j0 + u] = -1; }
                 else res[j0 + u] = act[u] ? q_answer<key_t, false>(P, PL, found[u], recs[u], pos[u], base[u], g) : -1;
             }
         }
         // ---- out[g] for the positions of the buffer ----
-        if (g0 + 16 <= P.n_bases) {
+        if constexpr (NODES) {
+            if (g0 + 16 <= P.n_bases) {                        // (g0 is a multiple of 16 and the arrays start 16-byte aligned)
+                ulonglong2* o = reinterpret_cast<ulonglong2*>(PL.out_node + g0);
+#pragma unroll
+                for (int q = 0; q < 8; q++) o[q] = make_ulonglong2(node[2 * q], node[2 * q + 1]);
+                if (PL.out_pos) {
+                    uint4* op = reinterpret_cast<uint4*>(PL.out_pos + g0);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) op[q] = make_uint4(npos[4 * q], npos[4 * q + 1], npos[4 * q + 2], npos[4 * q + 3]);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 16; j++) if (g0 + j < P.n_bases) { PL.out_node[g0 + j] = node[j]; if (PL.out_pos) PL.out_pos[g0 + j] = npos[j]; }
+            }
+        } else if (g0 + 16 <= P.n_bases) {
             int4* o = reinterpret_cast<int4*>(P.out + g0);     // (g0 is a multiple of 16 and the array starts 16-byte aligned)
 #pragma unroll
             for (int q = 0; q < 4; q++) o[q] = make_int4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
@@ -316,13 +343,15 @@ void q_fill_params(QParams& P, const QueryModel& M, const QueryIndex& ix)
 }
 
 int gkc_query_reads_run(gkc_ctx* c, const QueryModel& M, const QueryIndex& ix, const int32_t* const* planes, uint32_t nb_banks, const char* d_bases, const uint64_t* d_offsets,
-                        uint64_t n_reads, uint64_t n_bases, int32_t* d_out, int32_t* d_vectors, const char* who)
+                        uint64_t n_reads, uint64_t n_bases, int32_t* d_out, int32_t* d_vectors, const char* who, const QNodes* nodes)
 {
+    if (nodes) d_out = reinterpret_cast<int32_t*>(nodes->out_node);      // (the checks below are those of the one output every mode has)
     if (!d_offsets) GKC_FAIL(c, GKC_ERR_ARG, "%s: offsets are required", who);
     if (n_bases && (!d_bases || !d_out)) GKC_FAIL(c, GKC_ERR_ARG, "%s: bases and the output array are required", who);
-    if (((uintptr_t)d_bases & 15) != 0 || ((uintptr_t)d_out & 15) != 0) GKC_FAIL(c, GKC_ERR_ARG, "%s: d_bases and the output array must be 16-byte aligned", who);
+    if (((uintptr_t)d_bases & 15) != 0 || ((uintptr_t)d_out & 15) != 0 || (nodes && ((uintptr_t)nodes->out_pos & 15) != 0))
+        GKC_FAIL(c, GKC_ERR_ARG, "%s: d_bases and the output array%s must be 16-byte aligned", who, nodes ? "s" : "");
     if (n_bases >= (1ULL << 40)) GKC_FAIL(c, GKC_ERR_ARG, "%s: a single query is limited to 2^40 bases", who);
-    ScopedTimer tm(c, "query_reads");
+    ScopedTimer tm(c, nodes ? "graph_read_nodes" : "query_reads");
     const uint64_t n_tiles = (n_bases + QR_TILE - 1) / QR_TILE;
     // read-start bitmask (+ slack so every tile can read its halo words); the offsets check of gkc_push_reads_device in its last word
     const size_t rs_words = (size_t)(n_tiles * QR_TILE / 32 + 64);
@@ -341,8 +370,9 @@ int gkc_query_reads_run(gkc_ctx* c, const QueryModel& M, const QueryIndex& ix, c
     QPlanes PL{};
     if (planes) for (uint32_t p = 0; p < nb_banks && p < Q_MAX_BANKS; p++) PL.plane[p] = planes[p];
     const dim3 grid(q_grid(n_tiles)), block(QR_THREADS);
-    if (planes) { if (M.key_words == 1) hipLaunchKernelGGL((k_q_reads<1, true>), grid, block, 0, c->stream, P, PL); else hipLaunchKernelGGL((k_q_reads<2, true>), grid, block, 0, c->stream, P, PL); }
-    else        { if (M.key_words == 1) hipLaunchKernelGGL((k_q_reads<1, false>), grid, block, 0, c->stream, P, PL); else hipLaunchKernelGGL((k_q_reads<2, false>), grid, block, 0, c->stream, P, PL); }
+    if (nodes)       { if (M.key_words == 1) hipLaunchKernelGGL((k_q_reads<1, QM_NODES>), grid, block, 0, c->stream, P, *nodes); else hipLaunchKernelGGL((k_q_reads<2, QM_NODES>), grid, block, 0, c->stream, P, *nodes); }
+    else if (planes) { if (M.key_words == 1) hipLaunchKernelGGL((k_q_reads<1, QM_BANKS>), grid, block, 0, c->stream, P, PL); else hipLaunchKernelGGL((k_q_reads<2, QM_BANKS>), grid, block, 0, c->stream, P, PL); }
+    else             { if (M.key_words == 1) hipLaunchKernelGGL((k_q_reads<1, QM_COUNTS>), grid, block, 0, c->stream, P, PL); else hipLaunchKernelGGL((k_q_reads<2, QM_COUNTS>), grid, block, 0, c->stream, P, PL); }
     GKC_HIP(c, hipGetLastError());
     GKC_HIP(c, hipStreamSynchronize(c->stream));               // the mask goes back to the pool
     return GKC_OK;

@@ -19,6 +19,13 @@ struct QParams {
     int32_t* out; int32_t* vectors; uint32_t nb_banks;
 };
 
+// what k_q_reads answers per position: the abundance of the record found, the sum over the planes of a gkc_banks, or the record's place in the compacted graph
+constexpr int QM_COUNTS = 0, QM_BANKS = 1, QM_NODES = 2;
+// QM_NODES (gkc_paths.hip): the placement of the flat records (UnitigPlacement::unitig / pos) and the two outputs, u64[n_bases] and u32[n_bases] or NULL
+struct QNodes { const uint64_t* unitig; const uint32_t* pos; uint64_t* out_node; uint32_t* out_pos; };
+template <int MODE> struct QExtra { typedef QPlanes type; };  // the kernel's second argument
+template <> struct QExtra<QM_NODES> { typedef QNodes type; };
+
 template <typename K> __device__ __forceinline__ K q_load_key(const uint8_t* p) { return *reinterpret_cast<const K*>(p); }
 
 // order key of one m-mer given on the forward strand (A3: LUT semantics, restated like k_sample_exact)

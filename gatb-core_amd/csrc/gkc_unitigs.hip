@@ -216,8 +216,8 @@ static std::vector<std::pair<const void*, uint64_t>> ut_signature(const gkc_ctx*
     for (size_t d = 0; d < sig.size(); d++) sig[d] = {c->datasets[d].d_counts, c->datasets[d].n_solid};
     return sig;
 }
-// the guards of the queries, then: the placement describes the results the context holds now
-static int ut_require_placement(gkc_ctx* c, const char* who)
+// the guards of the queries, then: the placement describes the results the context holds now (also gkc_paths.hip)
+int ut_require_placement(gkc_ctx* c, const char* who)
 {
     GKC_TRY(q_prepare(c, who));
     UnitigPlacement& U = c->unitigs;

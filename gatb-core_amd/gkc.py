@@ -35,6 +35,7 @@ SYMBOLS = [
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
     "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
     "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove", "gkc_graph_simplify",
+    "gkc_graph_reads_nodes_device", "gkc_graph_reads_segments_device",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -86,6 +87,16 @@ class SimplifyRound(C.Structure):
 
 SIMPLIFY_KINDS = ("tips", "bulges", "ec")
 SIMPLIFY_LOG_CAP = 64 + 16 * 3 * 64                             # the most rounds a call can run
+
+
+class ReadSegment(C.Structure):
+    """gkc_read_segment (include/gkc.h): 24 bytes"""
+    _fields_ = [("node", C.c_uint64), ("read_pos", C.c_uint32), ("unitig_pos", C.c_uint32), ("n_kmers", C.c_uint32), ("pad", C.c_uint32)]
+
+
+# gkc_read_segment as a numpy record, and the sentinels of d_node (GKC_NODE_*)
+READ_SEGMENT = np.dtype([("node", np.uint64), ("read_pos", np.uint32), ("unitig_pos", np.uint32), ("n_kmers", np.uint32), ("pad", np.uint32)])
+NODE_REMOVED, NODE_ABSENT, NODE_NO_KMER = (1 << 64) - 1, (1 << 64) - 2, (1 << 64) - 3
 
 
 # gkc_read_abundance (include/gkc.h) as a numpy record
@@ -224,6 +235,8 @@ def lib():
         "gkc_graph_unitigs_build_alive": (C.c_int, [vp, vp, vp, P(u64), P(u64), P(u64)]),
         "gkc_graph_tips_remove": (C.c_int, [vp, vp, vp, P(TipParams), P(u64), vp, P(u64), P(u64), P(u64), P(u64)]),
         "gkc_graph_simplify": (C.c_int, [vp, vp, vp, P(SimplifyParams), P(SimplifyRound), u64, P(u64), P(u64), P(u64), P(u64), P(u64)]),
+        "gkc_graph_reads_nodes_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp]),
+        "gkc_graph_reads_segments_device": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64, P(u64), vp]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -727,7 +740,9 @@ class Counter:
         """ranks the solid records into unitigs and keeps the placement in the context -> (n_unitigs, n_bases, n_cycles). d_masks: device pointer to the masks
         neighbor_masks(d_out) wrote (None: computed inside)"""
         nu, nb, nc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._placement_nu = None
         self._chk(self.L.gkc_graph_unitigs_build(self.h, d_masks, C.byref(nu), C.byref(nb), C.byref(nc)))
+        self._placement_nu = nu.value
         return nu.value, nb.value, nc.value
 
     def unitigs_device(self, d_masks=None):
@@ -759,6 +774,77 @@ class Counter:
         u = u[: n.value].cpu().numpy().view(np.uint64)
         dead = u == np.uint64(M64)
         return np.where(dead, np.uint64(M64), u >> np.uint64(1)), ((u & np.uint64(1)) != 0) & ~dead, p[: n.value].cpu().numpy().view(np.uint32)
+
+    # ---- read paths (include/gkc.h, "read paths")
+    def read_nodes_device(self, d_bases, d_offsets, n_reads, n_bases, d_node, d_pos=None):
+        """where the reads lie: device pointers, d_bases, d_node and d_pos 16-byte aligned. d_node uint64[n_bases]: unitig << 1 | strand of the k-mer that starts at
+        each position, in the placement the context holds (unitigs_build, remove_tips, simplify), or NODE_REMOVED / NODE_ABSENT / NODE_NO_KMER; d_pos uint32[n_bases]
+        (or None): its position in the unitig"""
+        self._chk(self.L.gkc_graph_reads_nodes_device(self.h, d_bases, d_offsets, n_reads, n_bases, d_node, d_pos))
+
+    def read_segments_device(self, d_node, d_pos, d_offsets, n_reads, n_bases, d_seg_offsets=None, d_segments=None, cap_segments=0, d_support=None):
+        """the maximal runs of consecutive unitig positions inside each read, from what read_nodes_device wrote for the same offsets -> n_segments. d_seg_offsets
+        uint64[n_reads + 1] and d_segments READ_SEGMENT[cap_segments] both None: the count only. d_support: uint64[n_unitigs] or None"""
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_reads_segments_device(self.h, d_node, d_pos, d_offsets, n_reads, n_bases, d_seg_offsets, d_segments, cap_segments, C.byref(n), d_support))
+        return n.value
+
+    def _reads_to_device(self, bases, offsets):
+        """-> (bases tensor, offsets tensor, n_reads, n_bases); the bases padded so that an empty buffer still has an address"""
+        import torch
+        bases = np.ascontiguousarray(bases, dtype=np.uint8); offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offsets) < 1 or int(offsets[-1]) > len(bases):
+            raise GkcError("the offsets end beyond the bases")
+        nb = int(offsets[-1])
+        tb = torch.zeros(max(nb, 16), dtype=torch.uint8, device="cuda")
+        if nb:
+            tb[:nb] = torch.from_numpy(bases[:nb].copy()).cuda()
+        to = torch.from_numpy(offsets.view(np.int64).copy()).cuda()
+        return tb, to, len(offsets) - 1, nb
+
+    def _read_nodes_tensors(self, bases, offsets):
+        import torch
+        tb, to, nr, nb = self._reads_to_device(bases, offsets)
+        node = torch.zeros(max(nb, 2), dtype=torch.int64, device="cuda"); pos = torch.zeros(max(nb, 4), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        self.read_nodes_device(tb.data_ptr(), to.data_ptr(), nr, nb, node.data_ptr(), pos.data_ptr())
+        return to, nr, nb, node, pos
+
+    def read_nodes(self, bases, offsets):
+        """per position of the flat buffer, for the k-mer that starts there -> (unitig uint64[n_bases], strand bool[n_bases], pos uint32[n_bases], status uint8[n_bases]).
+        status 0: mapped — the k-mer as the read spells it is bases [pos, pos + k) of that unitig (strand False) or their reverse complement (strand True); 1: removed
+        (in the results, but of no unitig of the placement remove_tips / simplify left); 2: absent (a valid k-mer that is not in the results); 3: no k-mer starts
+        here. unitig is 2^64 - 1, strand False and pos 0 wherever status != 0."""
+        _, _, nb, node, pos = self._read_nodes_tensors(bases, offsets)
+        v = node[:nb].cpu().numpy().view(np.uint64)
+        status = np.zeros(nb, np.uint8)
+        status[v == np.uint64(NODE_REMOVED)] = 1; status[v == np.uint64(NODE_ABSENT)] = 2; status[v == np.uint64(NODE_NO_KMER)] = 3
+        mapped = status == 0
+        return (np.where(mapped, v >> np.uint64(1), np.uint64(M64)), ((v & np.uint64(1)) != 0) & mapped, pos[:nb].cpu().numpy().view(np.uint32), status)
+
+    def read_segments(self, bases, offsets, support=True):
+        """the unitigs every read spells -> (seg_offsets uint64[n_reads + 1], segments as a numpy record array of dtype READ_SEGMENT, support uint64[n_unitigs] or
+        None). Read r has segments[seg_offsets[r]: seg_offsets[r + 1]], ascending read_pos: node = unitig << 1 | strand, read_pos = the offset of the segment's first
+        k-mer inside the read, unitig_pos = that k-mer's position in the unitig, n_kmers consecutive positions (descending on strand 1). support[u] = the k-mers of
+        all reads that lie on unitig u. The nodes call, the sizing call and the fill, all on the device."""
+        import torch
+        to, nr, nb, node, pos = self._read_nodes_tensors(bases, offsets)
+        ns = self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb)
+        so = torch.zeros(nr + 1, dtype=torch.int64, device="cuda"); seg = torch.zeros(max(ns, 1) * READ_SEGMENT.itemsize, dtype=torch.uint8, device="cuda")
+        sup = None
+        if support:
+            # unitigs of the placement this object built last (unitigs_build, remove_tips, simplify set it). The nodes call above has just answered from the context's
+            # placement and fails after a recount, so a count that outlived its results never sizes the array
+            nu = getattr(self, "_placement_nu", None)
+            if nu is None:
+                raise GkcError("the placement in the context was not built through this object (unitigs_build, remove_tips or simplify first)")
+            sup = torch.zeros(max(nu, 1), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        got = self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb, so.data_ptr(), seg.data_ptr(), ns, sup.data_ptr() if support else None)
+        if got != ns:
+            raise GkcError("the fill found %d segments, the sizing call %d" % (got, ns))
+        return (so.cpu().numpy().view(np.uint64), seg.cpu().numpy()[: ns * READ_SEGMENT.itemsize].view(READ_SEGMENT).copy(),
+                sup[:nu].cpu().numpy().view(np.uint64) if support else None)
 
     # ---- links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
     def unitig_links_device(self, d_masks=None):
@@ -809,8 +895,9 @@ class Counter:
             self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
         per_round = np.zeros(max(1, min(max_rounds, 64)), np.uint64)
         nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
-        self._tips = None
+        self._tips = None; self._placement_nu = None
         self._chk(self.L.gkc_graph_tips_remove(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), C.byref(nr), _p(per_round), C.byref(rem), C.byref(nu), C.byref(nb), C.byref(nc)))
+        self._placement_nu = nu.value
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, tips_per_round=[int(x) for x in per_round[: nr.value]], records_removed=rem.value,
                     n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value)
@@ -845,9 +932,10 @@ class Counter:
                 self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
         log = (SimplifyRound * SIMPLIFY_LOG_CAP)()
         nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
-        self._tips = None
+        self._tips = None; self._placement_nu = None
         self._chk(self.L.gkc_graph_simplify(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), log, SIMPLIFY_LOG_CAP, C.byref(nr), C.byref(rem), C.byref(nu), C.byref(nb),
                                             C.byref(nc)))
+        self._placement_nu = nu.value
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, records_removed=rem.value, n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value,
                     log=[(SIMPLIFY_KINDS[e.kind], int(e.sweep), int(e.n_unitigs), int(e.n_hits), int(e.n_records_removed)) for e in log[: min(nr.value, SIMPLIFY_LOG_CAP)]])

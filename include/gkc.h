@@ -596,6 +596,43 @@ typedef struct gkc_simplify_round { uint32_t kind /* 0 tips, 1 bulges, 2 ec */, 
 int gkc_graph_simplify(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const gkc_simplify_params* params, gkc_simplify_round* log, uint64_t cap_log,
                        uint64_t* n_rounds, uint64_t* n_records_removed, uint64_t* n_unitigs, uint64_t* n_bases, uint64_t* n_cycles);
 
+/* ---- read paths: where the k-mers of reads lie in the compacted graph, and the unitigs a read spells, on the device ---------------------------------
+ * The join of "abundance queries" and "unitigs": the k-mers of a flat read buffer are searched in the results exactly as gkc_query_reads_device searches them, and
+ * the record found answers with its place in the placement the context holds — the plain build's, gkc_graph_unitigs_build_alive's, or the one gkc_graph_tips_remove /
+ * gkc_graph_simplify left. All terms are those of "unitigs": unitig u, L_u records, record i placed at (u, rev_i, p).
+ *   node   : g = index of the k-mer's FIRST base in the flat buffer, as in gkc_query_reads_device. f = the k-mer as the read spells it, c = min(f, revcomp(f)) = record i.
+ *            d_node[g] = u << 1 | strand, d_pos[g] = p, strand = rev_i XOR (f != c). strand 0: f equals bases [p, p + k) of unitig u as gkc_graph_unitigs_write emits it;
+ *            strand 1: f equals their reverse complement. A palindrome (even k) has f == c and takes the strand of its record: no special case.
+ *            GKC_NODE_REMOVED : c is a record of the results but of no unitig of this placement (what gkc_graph_unitigs_nodes reports as ~0: a dead record; only on a
+ *                               placement built over an alive array);
+ *            GKC_NODE_ABSENT  : a valid k-mer that is not in the results (gkc_query_reads_device: 0);
+ *            GKC_NODE_NO_KMER : no k-mer starts here (gkc_query_reads_device: -1).
+ *            d_pos[g] = 0 under a sentinel. Every value below GKC_NODE_NO_KMER that is no sentinel is a node.
+ *   segment: inside one read, position j CONTINUES position j - 1 when both carry a node, the two node values are equal (same unitig, same strand) and
+ *            pos_j == pos_{j-1} + 1 on strand 0, pos_j == pos_{j-1} - 1 on strand 1. The match is exact: there is no wrap around the cut of a cycle, a read that runs
+ *            round a cycle breaks there. A segment is a maximal run of such positions: node, read_pos = the offset of its first k-mer inside the read, unitig_pos = that
+ *            k-mer's position in the unitig, n_kmers = its length. The segments of a read are in ascending read_pos; d_seg_offsets is the CSR over the reads.
+ *   support: d_support[u] = the sum of n_kmers over all segments on u, either strand.
+ * State: the rules of the abundance queries, and for the nodes call (and for the segments call when d_support is given) a valid placement: GKC_ERR_ARG before a build
+ * or after the results changed, as for gkc_graph_unitigs_write. Offsets are checked as gkc_query_reads_device checks them; bad offsets touch no memory outside the
+ * buffers. Not served: the ranks of a communicator beyond the datasets a rank holds, and the merged state of a gkc_banks; whether consecutive segments of a read are
+ * joined by an edge of the link CSR (paths across links); the correction of the reads.
+ * Timing names of gkc_get_timing: "graph_read_nodes", "graph_read_segments" (the index: "query_index"). */
+#define GKC_NODE_REMOVED  (~0ull)        /* in the results, but a record of no unitig in this placement */
+#define GKC_NODE_ABSENT   (~0ull - 1)    /* a valid k-mer that is not in the results */
+#define GKC_NODE_NO_KMER  (~0ull - 2)    /* no k-mer starts here */
+/* d_bases, d_offsets, n_reads, n_bases: the arguments of gkc_query_reads_device, with its limits (d_bases 16-byte aligned, fewer than 2^40 bases). d_node: u64[n_bases],
+ * 16-byte aligned. d_pos: u32[n_bases], 16-byte aligned, or NULL (not written, not fetched). */
+int gkc_graph_reads_nodes_device(gkc_ctx* ctx, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases, uint64_t* d_node, uint32_t* d_pos);
+typedef struct gkc_read_segment { uint64_t node; uint32_t read_pos, unitig_pos, n_kmers, pad /* 0 */; } gkc_read_segment;   /* 24 bytes */
+/* d_node, d_pos: what gkc_graph_reads_nodes_device wrote for the same offsets (both required; they are read, never searched again: the call needs no counted results
+ * unless d_support is given). d_seg_offsets: u64[n_reads + 1]; d_segments: room for cap_segments; both NULL: only *n_segments is reported. Too small: GKC_ERR_CAPACITY,
+ * *n_segments reported, nothing written. A read of 2^32 bases or more: GKC_ERR_ARG. d_support: u64[n_unitigs of the context's placement] or NULL; zeroed and filled by
+ * a call that writes segments (not by the sizing call); a node that names no unitig of that placement (nodes of another placement): GKC_ERR_ARG, nothing written outside
+ * the array. No reads, or no bases: GKC_OK, every offset 0, *n_segments = 0. */
+int gkc_graph_reads_segments_device(gkc_ctx* ctx, const uint64_t* d_node, const uint32_t* d_pos, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                    uint64_t* d_seg_offsets, gkc_read_segment* d_segments, uint64_t cap_segments, uint64_t* n_segments, uint64_t* d_support);
+
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the
  * per-sequence copy into the flat buffer that gkc_push_reads takes. Same result as the reference reader for well-formed text:

@@ -6,7 +6,7 @@
 // window), so the neighbourhood of a solid k-mer is eight lookups and nothing has to be filtered.
 //
 //   k_graph_masks    : one thread per solid record of the whole result state (flat index in dataset order -> dataset by its QDs::base). The eight neighbours
-//                      (gr_shared_minima / gr_neighbour in gkc_graph.hpp, shared with gkc_unitigs.hip) are
+//                      (GrNode in gkc_graph.hpp, shared with the unitig, link and simplify kernels) are
 //                      made from the record's value x and ONE reverse complement rx: a right extension is ((x << 2) | j) & mask with reverse complement
 //                      (rx >> 2) | (comp(j) << 2(k-1)), a left extension the mirror image. A neighbour shares k-1 bases with x, so its minimizer is the minimum over the
 //                      k-m m-mers it shares with x and its one new m-mer: the order keys of x's m-mers are computed once (k-m+1 evaluations), the running minimum without
@@ -14,7 +14,8 @@
 //                      the canonical m-mer, the frequency table is built over canonical m-mers). GR_LOCKSTEP searches advance together like in k_q_reads.
 //   k_graph_topology : from the masks, in = popcount(mask >> 4), out = popcount(mask & 15). <false>: per tile of GR_TILE records the number of branching ones
 //                      (!(in == 1 && out == 1)) and the 5 x 5 table topology[in * 5 + out] (LDS table per workgroup, the dominant (1, 1) cell in a register, flushed once);
-//   k_graph_scan_sums: exclusive prefix of the tile sums by one workgroup (the scheme of the flag scan in gkc_banks.hip);
+//   k_graph_scan_tiles: exclusive prefix of the tile sums by one workgroup (the scheme of the flag scan in gkc_banks.hip), in place; behind gr_scan_tiles it serves every
+//                      scan of tile sums of the graph kernels (unitig numbering: two arrays in one launch; unitig links; read paths);
 //   k_graph_topology<true>: the branching records compacted in flat order (= dataset order, ascending inside a dataset) as Count records.
 // Element indices are 64-bit; grids are capped and the kernels stride.
 #include "gkc_graph.hpp"
@@ -24,19 +25,9 @@ template <int KW>
 __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t n_ds, uint64_t g0, uint64_t n, uint8_t* __restrict__ out)
 {
     typedef typename KeyT<KW>::type key_t;
-    constexpr int RB = 2 * (int)sizeof(key_t);
-    const uint32_t k = P.k, m = P.m;
-    const key_t kmask = KeyT<KW>::mask(k);
-    const uint32_t top = 2u * (k - 1);                         // bit position of a k-mer's first nucleotide
+    GrNode<KW> N(P);
     for (uint64_t i = (uint64_t)blockIdx.x * GR_THREADS + threadIdx.x; i < n; i += (uint64_t)gridDim.x * GR_THREADS) {
-        const uint64_t g = g0 + i;
-        const QDs D = P.ds[gr_dataset_of(P.ds, n_ds, g)];
-        const key_t x = q_load_key<key_t>(D.recs + (g - D.base) * (uint64_t)RB);
-        const key_t rx = KeyT<KW>::revcomp(x, k);
-        uint32_t min_r, min_l;
-        gr_shared_minima<key_t>(P, x, min_r, min_l);
-        const uint32_t suf = (uint32_t)x & (P.mmask >> 2);                    // the last / the first m-1 nucleotides of x
-        const uint32_t pre = (uint32_t)(x >> (2u * (k - m + 1)));
+        N.load(P, n_ds, g0 + i);
         uint32_t res = 0;
 #pragma unroll 1
         for (uint32_t e0 = 0; e0 < 8; e0 += GR_LOCKSTEP) {
@@ -45,11 +36,11 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t 
 #pragma unroll
             for (int u = 0; u < GR_LOCKSTEP; u++) {
                 key_t fw, rv;
-                gr_neighbour<key_t>(P, x, rx, kmask, top, suf, pre, min_r, min_l, e0 + (uint32_t)u, fw, rv, d[u]);
+                N.neighbour(P, e0 + (uint32_t)u, fw, rv, d[u]);
                 key[u] = fw < rv ? fw : rv;                    // Model.hpp:294
                 act[u] = true;
             }
-            q_search<key_t, RB, GR_LOCKSTEP>(P, act, d, key, found, pos, recs, base);
+            q_search<key_t, GrNode<KW>::RB, GR_LOCKSTEP>(P, act, d, key, found, pos, recs, base);
 #pragma unroll
             for (int u = 0; u < GR_LOCKSTEP; u++) res |= (uint32_t)found[u] << (e0 + (uint32_t)u);
         }
@@ -59,9 +50,8 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_masks(QParams P, uint32_t 
 
 // ------------------------------------------------------------------------------------------------ topology, branching nodes
 template <int KW, bool GATHER>
-__global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __restrict__ masks, uint64_t n, uint32_t n_tiles, uint32_t* __restrict__ sums,
-                                                                unsigned long long* __restrict__ topo, const uint64_t* __restrict__ offs, const QDs* __restrict__ ds, uint32_t n_ds,
-                                                                uint8_t* __restrict__ records, uint64_t cap)
+__global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __restrict__ masks, uint64_t n, uint32_t n_tiles, uint64_t* __restrict__ offs /* <false>: the tile sums out */,
+                                                                unsigned long long* __restrict__ topo, const QDs* __restrict__ ds, uint32_t n_ds, uint8_t* __restrict__ records, uint64_t cap)
 {
     typedef typename KeyT<KW>::type key_t;
     constexpr int RB = 2 * (int)sizeof(key_t);
@@ -83,7 +73,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __
         }
         uint32_t tot;
         const uint32_t ex = gr_block_excl(s, s_w, &tot);
-        if (!GATHER) { if (threadIdx.x == 0) sums[t] = tot; }
+        if (!GATHER) { if (threadIdx.x == 0) offs[t] = tot; }
         else {
             uint64_t p = offs[t] + ex;
 #pragma unroll
@@ -111,25 +101,28 @@ __global__ __launch_bounds__(GR_THREADS) void k_graph_topology(const uint8_t* __
         if (threadIdx.x < 25 && s_topo[threadIdx.x]) atomicAdd(&topo[threadIdx.x], s_topo[threadIdx.x]);
     }
 }
-// one workgroup: offs[t] = sums[0] + ... + sums[t - 1], offs[n_tiles] = everything; GR_THREADS sums at a time, the carry in 64 bits
-__global__ __launch_bounds__(GR_THREADS) void k_graph_scan_sums(const uint32_t* __restrict__ sums, uint32_t n_tiles, uint64_t* __restrict__ offs)
+// one workgroup: the exclusive prefix of the tile sums a[0, n_tiles) in place, a[n_tiles] = everything, GR_THREADS sums at a time; then the same for b unless it is NULL
+__global__ __launch_bounds__(GR_THREADS) void k_graph_scan_tiles(uint64_t* __restrict__ a, uint64_t* __restrict__ b, uint32_t n_tiles)
 {
-    __shared__ uint32_t s_w[GR_THREADS / 64];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n_tiles; base += GR_THREADS) {
-        const uint32_t t = base + threadIdx.x;
-        const uint32_t v = t < n_tiles ? sums[t] : 0u;
-        uint32_t tot;
-        const uint32_t ex = gr_block_excl(v, s_w, &tot);
-        if (t < n_tiles) offs[t] = carry + ex;
-        carry += tot;
-        if (n_tiles - base <= GR_THREADS) break;               // (base + GR_THREADS may wrap at the top of the 32-bit range)
+    __shared__ uint64_t s_w[GR_THREADS / 64];
+    for (uint64_t* sums = a; sums; sums = sums == a ? b : nullptr) {
+        uint64_t carry = 0;
+        for (uint32_t base = 0; base < n_tiles; base += GR_THREADS) {
+            const uint32_t t = base + threadIdx.x;
+            const uint64_t v = t < n_tiles ? sums[t] : 0ull;
+            uint64_t tot;
+            const uint64_t ex = gr_block_excl<uint64_t>(v, s_w, &tot);
+            if (t < n_tiles) sums[t] = carry + ex;
+            carry += tot;
+            if (n_tiles - base <= GR_THREADS) break;           // (base + GR_THREADS may wrap at the top of the 32-bit range)
+        }
+        if (threadIdx.x == 0) sums[n_tiles] = carry;
     }
-    if (threadIdx.x == 0) offs[n_tiles] = carry;
 }
 
 // ------------------------------------------------------------------------------------------------ host side
 uint64_t gr_total(const gkc_ctx* c) { uint64_t t = 0; for (const Dataset& D : c->datasets) t += D.n_solid; return t; }
+void gr_scan_tiles(gkc_ctx* c, uint64_t* a, uint64_t* b, uint32_t n_tiles) { hipLaunchKernelGGL(k_graph_scan_tiles, dim3(1), dim3(GR_THREADS), 0, c->stream, a, b, n_tiles); }
 
 // masks of the records [g0, g0 + n) of the flat order into d_masks[0, n); q_prepare has run
 int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks)
@@ -138,8 +131,7 @@ int gr_masks_run(gkc_ctx* c, uint64_t g0, uint64_t n, uint8_t* d_masks)
     QParams P{}; q_fill_params(P, q_model_of(c), c->qidx);
     const uint32_t n_ds = (uint32_t)c->datasets.size();
     const dim3 grid(q_grid((n + GR_THREADS - 1) / GR_THREADS)), block(GR_THREADS);
-    if (c->key_words == 1) hipLaunchKernelGGL((k_graph_masks<1>), grid, block, 0, c->stream, P, n_ds, g0, n, d_masks);
-    else                   hipLaunchKernelGGL((k_graph_masks<2>), grid, block, 0, c->stream, P, n_ds, g0, n, d_masks);
+    GR_BY_KEY_WIDTH(c, hipLaunchKernelGGL((k_graph_masks<KW>), grid, block, 0, c->stream, P, n_ds, g0, n, d_masks));
     GKC_HIP(c, hipGetLastError());
     GKC_HIP(c, hipStreamSynchronize(c->stream));
     return GKC_OK;
@@ -186,23 +178,20 @@ int gkc_graph_branching_solid(gkc_ctx* c, const uint8_t* d_masks, void* d_record
     const uint64_t n_tiles64 = (total + GR_TILE - 1) / GR_TILE;
     if (n_tiles64 >= (1ull << 32)) GKC_FAIL(c, GKC_ERR_ARG, "gkc_graph_branching_solid: more than 2^32 tiles of %d k-mers", GR_TILE);
     const uint32_t n_tiles = (uint32_t)n_tiles64, n_ds = (uint32_t)c->datasets.size();
-    DevBuf tmp, d_sums, d_offs, d_topo;
+    DevBuf tmp, d_offs, d_topo;
     if (!d_masks) { GKC_TRY(c->ensure(tmp, (size_t)total)); GKC_TRY(gr_masks_run(c, 0, total, (uint8_t*)tmp.p)); d_masks = (const uint8_t*)tmp.p; }
-    GKC_TRY(c->ensure(d_sums, (size_t)n_tiles * 4)); GKC_TRY(c->ensure(d_offs, ((size_t)n_tiles + 1) * 8)); GKC_TRY(c->ensure(d_topo, 25 * 8));
+    GKC_TRY(c->ensure(d_offs, ((size_t)n_tiles + 1) * 8)); GKC_TRY(c->ensure(d_topo, 25 * 8));
     uint64_t n_br = 0, topo[25];
     {
         ScopedTimer tm(c, "graph_branching");
         const QDs* ds = (const QDs*)c->qidx.table.p;
         const dim3 grid(q_grid(n_tiles)), block(GR_THREADS);
-        const bool wide = c->key_words != 1;
+        uint64_t* offs = (uint64_t*)d_offs.p;                  // the tile sums, then their exclusive prefix
         GKC_HIP(c, hipMemsetAsync(d_topo.p, 0, 25 * 8, c->stream));
-        if (!wide) hipLaunchKernelGGL((k_graph_topology<1, false>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)d_sums.p, (unsigned long long*)d_topo.p, (const uint64_t*)nullptr, ds, n_ds, (uint8_t*)nullptr, (uint64_t)0);
-        else       hipLaunchKernelGGL((k_graph_topology<2, false>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)d_sums.p, (unsigned long long*)d_topo.p, (const uint64_t*)nullptr, ds, n_ds, (uint8_t*)nullptr, (uint64_t)0);
-        hipLaunchKernelGGL(k_graph_scan_sums, dim3(1), block, 0, c->stream, (const uint32_t*)d_sums.p, n_tiles, (uint64_t*)d_offs.p);
-        if (d_records && cap_records) {
-            if (!wide) hipLaunchKernelGGL((k_graph_topology<1, true>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const uint64_t*)d_offs.p, ds, n_ds, (uint8_t*)d_records, cap_records);
-            else       hipLaunchKernelGGL((k_graph_topology<2, true>), grid, block, 0, c->stream, d_masks, total, n_tiles, (uint32_t*)nullptr, (unsigned long long*)nullptr, (const uint64_t*)d_offs.p, ds, n_ds, (uint8_t*)d_records, cap_records);
-        }
+        GR_BY_KEY_WIDTH(c, hipLaunchKernelGGL((k_graph_topology<KW, false>), grid, block, 0, c->stream, d_masks, total, n_tiles, offs, (unsigned long long*)d_topo.p, ds, n_ds, (uint8_t*)nullptr, (uint64_t)0));
+        gr_scan_tiles(c, offs, nullptr, n_tiles);
+        if (d_records && cap_records)
+            GR_BY_KEY_WIDTH(c, hipLaunchKernelGGL((k_graph_topology<KW, true>), grid, block, 0, c->stream, d_masks, total, n_tiles, offs, (unsigned long long*)nullptr, ds, n_ds, (uint8_t*)d_records, cap_records));
         GKC_HIP(c, hipGetLastError());
         GKC_HIP(c, hipMemcpyAsync(&n_br, (const uint64_t*)d_offs.p + n_tiles, 8, hipMemcpyDeviceToHost, c->stream));
         GKC_HIP(c, hipMemcpyAsync(topo, d_topo.p, 25 * 8, hipMemcpyDeviceToHost, c->stream));

@@ -8,8 +8,7 @@
 //                    never a search of the offsets —, another node, or a position that is not the neighbour's); it STARTS a segment when it breaks and carries a node. Two
 //                    ballots per wave: start[w], brk[w]. Positions behind the buffer break and start nothing; one more word behind the last one does the same, so that
 //                    every walk below ends inside the arrays.
-//   k_path_tiles   : the starts of every tile of GR_TILE words; k_path_scan: exclusive prefix of the tile sums by one workgroup (the scheme of k_unitig_link_scan);
-//   k_path_ranks   : rank[w] = the starts in front of word w. The number of starts in front of position g is rank[g >> 6] + popcount(start[g >> 6] below bit g & 63):
+//   k_graph_tile_sums, gr_scan_tiles, k_graph_tile_offsets<false> (gkc_graph.hpp) over the starts per word: rank[w] = the starts in front of word w. The number of starts in front of position g is rank[g >> 6] + popcount(start[g >> 6] below bit g & 63):
 //                    that is the index of a segment among all segments, and at g = offsets[r] it is seg_offsets[r] — the CSR over the reads needs no pass over the reads'
 //                    counts, and no scan of its own (k_path_offsets: one thread per entry).
 //   k_path_fill    : a lane whose position starts a segment writes it at that index. Its length is the distance to the next break: the rest of brk[w], then whole words
@@ -18,7 +17,7 @@
 //                    (offsets[0] == 0 was checked). d_support takes one 64-bit vector atomic per segment.
 // Element indices are 64-bit; grids go through q_grid and the kernels stride. Scratch comes from the context's pool on c->stream, is allocated before the first launch
 // and synchronised before it goes back.
-#include "gkc_graph.hpp"
+#include "gkc_unitigs.hpp"
 
 constexpr int PT_WAVES = GR_THREADS / 64;                     // words of 64 positions a workgroup handles per trip
 
@@ -48,51 +47,7 @@ __global__ __launch_bounds__(GR_THREADS) void k_path_bits(const uint64_t* __rest
         if (lane == 0) { start[w] = sb; brk[w] = bb; }
     }
 }
-// the starts of the words [0, n_w) per tile of GR_TILE words
-__global__ __launch_bounds__(GR_THREADS) void k_path_tiles(const uint64_t* __restrict__ start, uint64_t n_w, uint32_t n_tiles, uint64_t* __restrict__ tile_sum)
-{
-    __shared__ uint64_t s_w[GR_THREADS / 64];
-    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const uint64_t i0 = (uint64_t)t * GR_TILE + (uint64_t)threadIdx.x * GR_PER_THREAD;
-        uint64_t sum = 0;
-#pragma unroll
-        for (uint32_t r = 0; r < GR_PER_THREAD; r++) sum += i0 + r < n_w ? (uint64_t)__popcll(start[i0 + r]) : 0ull;
-        uint64_t tot;
-        gr_block_excl<uint64_t>(sum, s_w, &tot);
-        if (threadIdx.x == 0) tile_sum[t] = tot;
-    }
-}
-// one workgroup: the exclusive prefix of the tile sums in place, [n_tiles] = everything
-__global__ __launch_bounds__(GR_THREADS) void k_path_scan(uint64_t* __restrict__ tile_sum, uint32_t n_tiles)
-{
-    __shared__ uint64_t s_w[GR_THREADS / 64];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < n_tiles; base += GR_THREADS) {
-        const uint32_t t = base + threadIdx.x;
-        const uint64_t v = t < n_tiles ? tile_sum[t] : 0ull;
-        uint64_t tot;
-        const uint64_t e = gr_block_excl<uint64_t>(v, s_w, &tot);
-        if (t < n_tiles) tile_sum[t] = carry + e;
-        carry += tot;
-        if (n_tiles - base <= GR_THREADS) break;               // (base + GR_THREADS may wrap at the top of the 32-bit range)
-    }
-    if (threadIdx.x == 0) tile_sum[n_tiles] = carry;
-}
-__global__ __launch_bounds__(GR_THREADS) void k_path_ranks(const uint64_t* __restrict__ start, uint64_t n_w, uint32_t n_tiles, const uint64_t* __restrict__ tile_off,
-                                                            uint64_t* __restrict__ rank)
-{
-    __shared__ uint64_t s_w[GR_THREADS / 64];
-    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const uint64_t i0 = (uint64_t)t * GR_TILE + (uint64_t)threadIdx.x * GR_PER_THREAD;
-        uint32_t v[GR_PER_THREAD]; uint64_t sum = 0;
-#pragma unroll
-        for (uint32_t r = 0; r < GR_PER_THREAD; r++) { v[r] = i0 + r < n_w ? (uint32_t)__popcll(start[i0 + r]) : 0u; sum += v[r]; }
-        uint64_t tot;
-        uint64_t o = tile_off[t] + gr_block_excl<uint64_t>(sum, s_w, &tot);
-#pragma unroll
-        for (uint32_t r = 0; r < GR_PER_THREAD; r++) { if (i0 + r < n_w) rank[i0 + r] = o; o += v[r]; }
-    }
-}
+struct PtWordStarts { const uint64_t* start; __device__ __forceinline__ uint32_t operator()(uint64_t w) const { return (uint32_t)__popcll(start[w]); } };      // the value of a word in the prefix sum
 // offsets[r] <= n_bases was checked: its word is at most word n_words, which both arrays have
 __global__ __launch_bounds__(256) void k_path_offsets(const uint64_t* __restrict__ offsets, uint64_t n_entries, const uint64_t* __restrict__ rank, const uint64_t* __restrict__ start,
                                                        uint64_t* __restrict__ seg_offsets)
@@ -192,8 +147,8 @@ int gkc_graph_reads_segments_device(gkc_ctx* c, const uint64_t* d_node, const ui
     // ---- starts and breaks, the number of segments
     if (n_bases) {
         hipLaunchKernelGGL(k_path_bits, words, block, 0, c->stream, d_node, d_pos, (const uint32_t*)rs, n_bases, n_words, start, brk);
-        hipLaunchKernelGGL(k_path_tiles, tiles, block, 0, c->stream, (const uint64_t*)start, n_w, n_tiles, ts);
-        hipLaunchKernelGGL(k_path_scan, dim3(1), block, 0, c->stream, ts, n_tiles);
+        hipLaunchKernelGGL(k_graph_tile_sums<PtWordStarts>, tiles, block, 0, c->stream, PtWordStarts{start}, n_w, n_tiles, ts);
+        gr_scan_tiles(c, ts, nullptr, n_tiles);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&total, ts + n_tiles, 8, hipMemcpyDeviceToHost, c->stream);
         es = hipStreamSynchronize(c->stream);
@@ -208,7 +163,7 @@ int gkc_graph_reads_segments_device(gkc_ctx* c, const uint64_t* d_node, const ui
     if (d_support && n_unitigs) e = hipMemsetAsync(d_support, 0, (size_t)n_unitigs * 8, c->stream);
     if (e == hipSuccess && !n_bases) e = hipMemsetAsync(d_seg_offsets, 0, (size_t)(n_reads + 1) * 8, c->stream);
     if (e == hipSuccess && n_bases) {
-        hipLaunchKernelGGL(k_path_ranks, tiles, block, 0, c->stream, (const uint64_t*)start, n_w, n_tiles, (const uint64_t*)ts, rank);
+        hipLaunchKernelGGL((k_graph_tile_offsets<false, PtWordStarts>), tiles, block, 0, c->stream, PtWordStarts{start}, n_w, n_tiles, (const uint64_t*)ts, rank);
         hipLaunchKernelGGL(k_path_offsets, dim3(q_grid((n_reads + 1 + 255) / 256)), dim3(256), 0, c->stream, d_offsets, n_reads + 1, (const uint64_t*)rank, (const uint64_t*)start, d_seg_offsets);
         if (total) hipLaunchKernelGGL(k_path_fill, words, block, 0, c->stream, d_node, d_pos, (const uint32_t*)rs, n_words, (const uint64_t*)start, (const uint64_t*)brk, (const uint64_t*)rank,
                                       d_segments, (unsigned long long*)d_support, n_unitigs, d_flags + 2);

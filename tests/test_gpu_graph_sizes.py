@@ -1,4 +1,4 @@
-"""The graph kernels past one grid pass (csrc/gkc_graph.hip, csrc/gkc_unitigs.hip: "grids are capped and the kernels stride"). The launch geometry: thread-per-element
+"""The graph kernels past one grid pass (csrc/gkc_graph.hip, csrc/gkc_unitigs.hip, csrc/gkc_unitig_links.hip, csrc/gkc_simplify.hip: "grids are capped and the kernels stride"). The launch geometry: thread-per-element
 grids are capped at 2048 workgroups of 256 threads and stride above 524,288 elements (records, unitigs, slots; the ranking runs over 2 n states: n > 262,144); the three
 one-workgroup scans take 256 tile sums of 1024 elements per trip and carry a running total above 262,144 records (the link scan: above 131,072 unitigs, two slots each);
 the tile kernels stride above 2048 tiles (n > 2,097,152 records, the link tile kernels above 1,048,576 unitigs). The other graph tests stay below 6 * 10^4 records. Here
@@ -235,7 +235,7 @@ def test_tips_past_one_pass_and_a_resumed_simplify(gkc, simplified):
     got = c.remove_tips(**TOPO)
     assert got["tips_per_round"] == [STRUCTURES["tips"], 0] and got["rounds"] == 2 and got["records_removed"] == STRUCTURES["tips"]
     s.assert_state(c, got, ("tips",))
-    # the state remove_tips left, resumed (k_alive_check over more than one pass): the log of the whole call without its first round
+    # the state remove_tips left, resumed (k_alive_count with the masks, over more than one pass): the log of the whole call without its first round
     p = simplify_defaults(K, **TOPO)
     log, alive = gi.expected_simplify_log(s.b, s.values, s.ab, p, s.n_unitigs)
     got = c.simplify(resume=True, **TOPO)

@@ -1,4 +1,4 @@
-"""Simplification of the compacted graph on the device (csrc/gkc_unitigs.hip: gkc_graph_simplify; gkc.Counter.simplify, remove_bulges, remove_erroneous_connections).
+"""Simplification of the compacted graph on the device (csrc/gkc_simplify.hip: gkc_graph_simplify; gkc.Counter.simplify, remove_bulges, remove_erroneous_connections).
 Expected values: the statement of tests/test_simplify_cpu.py, which recomputes unitigs and links from scratch over the alive values every round and is pinned there by
 the reference's own bubble and EC tests — alive, masks, the log of every round, bases / offsets / KC, the placement of every record and the link CSR, byte for byte.
 Run with `pytest -m gpu`."""

@@ -1,4 +1,4 @@
-"""Tip removal on the device (csrc/gkc_unitigs.hip: gkc_graph_tips_remove, gkc_graph_unitigs_build_alive; gkc.Counter.remove_tips, simplified_unitigs).
+"""Tip removal on the device (csrc/gkc_simplify.hip: gkc_graph_tips_remove; csrc/gkc_unitigs.hip: gkc_graph_unitigs_build_alive; gkc.Counter.remove_tips, simplified_unitigs).
 Expected values: the statement of tests/test_tips_cpu.py, which recomputes unitigs and links from scratch over the alive values every round and is pinned there by the
 reference's own tip test — alive, masks, tips per round, bases / offsets / KC, the placement of every record and the link CSR, byte for byte.
 Run with `pytest -m gpu`."""

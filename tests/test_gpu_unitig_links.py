@@ -1,4 +1,4 @@
-"""Links between the unitigs on the device (csrc/gkc_unitigs.hip: gkc_graph_unitigs_links; gkc.Counter.unitig_links, unitig_links_device, write_unitigs_fasta).
+"""Links between the unitigs on the device (csrc/gkc_unitig_links.hip: gkc_graph_unitigs_links; gkc.Counter.unitig_links, unitig_links_device, write_unitigs_fasta).
 Expected values: statement A of tests/test_unitig_links_cpu.py (the definition over the masks and the placement, pinned there by the reference's own links of one input
 and by statement B, the overlaps of the sequences) — offsets and entries element for element — and the reference's digest itself. Every comparison is exact.
 Run with `pytest -m gpu`."""

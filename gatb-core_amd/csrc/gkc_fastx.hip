@@ -8,11 +8,15 @@
 // The reference reader is a sequential state machine; for WELL-FORMED files its result is a function of the line structure:
 //   FASTA : a line whose first character is '>' or '@' is a header; every other line is appended to the current sequence up to its
 //           '\n'; one trailing '\r' is dropped when the accumulated sequence is longer than 1 character (BankFasta.cpp:479);
+//           a lone '\r' that is the unterminated last byte of the text is KEPT (">a\nAC\n\r" reads "AC\r"): the reference takes it with
+//           buffered_getc, and buffered_gets then returns -1 at end of input before its strip step (BankFasta.cpp:433). The reference's
+//           own answer there depends on whether the file size is a multiple of its read buffer (end of file is only flagged by a short
+//           read); the oracle and this parser state the general case, end of file already flagged;
 //   FASTQ : records of exactly four lines (header, sequence, '+', quality). The reference consumes the quality BY LENGTH
 //           (BankFasta.cpp:556): that equals "one line" iff the quality line is at least as long as the sequence line.
 // Everything the line model cannot express exactly (a sequence line starting with '+' in a FASTA file, multi-line FASTQ, a quality
 // shorter than its sequence, '>' / '@' inside the lines before the first header) is REFUSED with GKC_ERR_FORMAT — no approximation, no
-// host fallback. Parity: tests/test_gpu_fastx.py against the CPU restatement of the character state machine, which is pinned on the
+// host fallback. Parity: tests/test_gpu_fastx.py and tests/test_gpu_input_sizes.py (features at every phase of a tile border) against the CPU restatement of the character state machine, which is pinned on the
 // reference's own bank fixtures (tests/golden/bank, known answers of test/unit/src/bank/TestBank.cpp).
 //
 // Device algorithm (all passes stream the text with 16-byte loads, 4096-byte tiles, 256 threads):
@@ -205,7 +209,8 @@ __global__ void k_fx_classify(const uint8_t* __restrict__ text, const uint64_t* 
                 kd = FXK_SEQ;
                 if (text[ls + len - 1] == '\r') {
                     bool strip = len > 1;
-                    if (!strip) {                                  // a line that is exactly "\r": dropped unless it is the first non-empty line of its record
+                    if (!strip && ls + 1 != n_text) {              // a line that is exactly "\r": dropped unless it is the first non-empty line of its record, or the
+                                                                   // unterminated last byte of the text (the reference is at end of input before its strip step)
                         for (uint64_t q = j; q-- > h0;) {
                             const uint64_t l2 = fx_len(line_start, q);
                             if (l2 && fx_is_hdr(text[line_start[q]])) break;

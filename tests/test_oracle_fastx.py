@@ -57,4 +57,6 @@ def test_reader_rules():
     assert f(b"@r1\nACGT\n+\nII\nII\n@r2\nGG\n+\nII\n") == [b"ACGT", b"GG"]        # multi-line quality, consumed by length
     assert f(b"@r1\nACGT\n+\nII\n@r2\nGG\n+\nII\n") == [b"ACGT"]                   # short quality swallows the next header line (reference behaviour)
     assert f(b">a\nAC GT\n") == [b"AC GT"]                                         # blanks inside a sequence line are kept
+    assert f(b">a\nAC\n\r") == [b"AC\r"] and f(b">a\nAC\r\n\r") == [b"AC\r"]            # a lone \r as the unterminated last line is kept: buffered_gets is at end of input before its strip step (:433)
+    assert f(b">a\nAC\n\r\n") == [b"AC"]                                           # ... terminated, it is dropped like any trailing \r
     assert f(b"") == [] and f(b"\n\n") == [] and f(b">") == [] and f(b">x") == [b""]

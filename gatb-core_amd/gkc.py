@@ -35,7 +35,7 @@ SYMBOLS = [
     "gkc_graph_neighbors_solid", "gkc_graph_neighbors_partition", "gkc_graph_branching_solid",
     "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
     "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove", "gkc_graph_simplify",
-    "gkc_graph_reads_nodes_device", "gkc_graph_reads_segments_device",
+    "gkc_graph_reads_nodes_device", "gkc_graph_reads_segments_device", "gkc_graph_reads_walks_device",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -97,6 +97,16 @@ class ReadSegment(C.Structure):
 # gkc_read_segment as a numpy record, and the sentinels of d_node (GKC_NODE_*)
 READ_SEGMENT = np.dtype([("node", np.uint64), ("read_pos", np.uint32), ("unitig_pos", np.uint32), ("n_kmers", np.uint32), ("pad", np.uint32)])
 NODE_REMOVED, NODE_ABSENT, NODE_NO_KMER = (1 << 64) - 1, (1 << 64) - 2, (1 << 64) - 3
+
+
+class ReadWalk(C.Structure):
+    """gkc_read_walk (include/gkc.h): 16 bytes"""
+    _fields_ = [("first_segment", C.c_uint64), ("n_segments", C.c_uint32), ("n_kmers", C.c_uint32)]
+
+
+# gkc_read_walk as a numpy record, and the values of a junction that are no link index (GKC_JUNCTION_*)
+READ_WALK = np.dtype([("first_segment", np.uint64), ("n_segments", np.uint32), ("n_kmers", np.uint32)])
+JUNCTION_END, JUNCTION_BREAK, JUNCTION_COLLINEAR, JUNCTION_UNLINKED = (1 << 64) - 1, (1 << 64) - 2, (1 << 64) - 3, (1 << 64) - 4
 
 
 # gkc_read_abundance (include/gkc.h) as a numpy record
@@ -237,6 +247,7 @@ def lib():
         "gkc_graph_simplify": (C.c_int, [vp, vp, vp, P(SimplifyParams), P(SimplifyRound), u64, P(u64), P(u64), P(u64), P(u64), P(u64)]),
         "gkc_graph_reads_nodes_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp]),
         "gkc_graph_reads_segments_device": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64, P(u64), vp]),
+        "gkc_graph_reads_walks_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, vp, u64, P(u64), vp]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -740,7 +751,7 @@ class Counter:
         """ranks the solid records into unitigs and keeps the placement in the context -> (n_unitigs, n_bases, n_cycles). d_masks: device pointer to the masks
         neighbor_masks(d_out) wrote (None: computed inside)"""
         nu, nb, nc = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._placement_nu = None
+        self._placement_nu = None; self._placement_masks = None      # (the plain build: its masks are those of the results, read_walks computes them when it needs them)
         self._chk(self.L.gkc_graph_unitigs_build(self.h, d_masks, C.byref(nu), C.byref(nb), C.byref(nc)))
         self._placement_nu = nu.value
         return nu.value, nb.value, nc.value
@@ -846,6 +857,51 @@ class Counter:
         return (so.cpu().numpy().view(np.uint64), seg.cpu().numpy()[: ns * READ_SEGMENT.itemsize].view(READ_SEGMENT).copy(),
                 sup[:nu].cpu().numpy().view(np.uint64) if support else None)
 
+    def read_walks_device(self, d_seg_offsets, d_segments, n_reads, n_segments, d_link_offsets, d_links, n_links, d_junction=None, d_walk_offsets=None, d_walks=None,
+                          cap_walks=0, d_link_support=None):
+        """the segments of every read joined across the links of the compacted graph, from what read_segments_device and gkc_graph_unitigs_links wrote for the placement
+        the context holds -> n_walks. d_walk_offsets uint64[n_reads + 1] and d_walks READ_WALK[cap_walks] both None: the count only. d_junction: uint64[n_segments] or
+        None; d_link_support: uint64[n_links] or None"""
+        n = C.c_uint64()
+        self._chk(self.L.gkc_graph_reads_walks_device(self.h, d_seg_offsets, d_segments, n_reads, n_segments, d_link_offsets, d_links, n_links, d_junction, d_walk_offsets, d_walks,
+                                                      cap_walks, C.byref(n), d_link_support))
+        return n.value
+
+    def read_walks(self, bases, offsets, link_support=True):
+        """the paths in the compacted graph every read spells -> dict: seg_offsets, segments (as read_segments gives them), junction uint64[n_segments] (per segment its
+        relation to the next segment of the same read: the index into links of the link it follows, or JUNCTION_END / BREAK / COLLINEAR / UNLINKED), walk_offsets
+        uint64[n_reads + 1], walks (numpy record array of dtype READ_WALK: first_segment, n_segments, n_kmers — a maximal chain of segments joined by links; it spells
+        n_kmers + k - 1 bases of the read from its first segment's read_pos), link_offsets, links (as unitig_links gives them, of the placement this object built last:
+        unitigs_build, remove_tips or simplify), link_support uint64[n_links] or None: the reads crossing every link entry, raw (the other direction counts on the mirror
+        entry). The nodes call, the segments calls, the link calls and the walks calls, all on the device."""
+        import torch
+        to, nr, nb, node, pos = self._read_nodes_tensors(bases, offsets)
+        nu = getattr(self, "_placement_nu", None)
+        if nu is None:
+            raise GkcError("the placement in the context was not built through this object (unitigs_build, remove_tips or simplify first)")
+        ns = self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb)
+        so = torch.zeros(nr + 1, dtype=torch.int64, device="cuda"); seg = torch.zeros(max(ns, 1) * READ_SEGMENT.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        if self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb, so.data_ptr(), seg.data_ptr(), ns) != ns:
+            raise GkcError("the fill found another number of segments than the sizing call")
+        # the masks the placement was built from: those remove_tips / simplify left, or the plain ones (computed once for the two link calls)
+        masks = getattr(self, "_placement_masks", None)
+        keep, d_masks = self._masks_once(None if masks is None else masks.data_ptr())
+        lo, links = self._unitig_links_of_placement(nu, d_masks)
+        nl = len(links)
+        args = (so.data_ptr(), seg.data_ptr(), nr, ns, lo.data_ptr(), links.data_ptr(), nl)
+        nw = self.read_walks_device(*args)
+        jn = torch.zeros(max(ns, 1), dtype=torch.int64, device="cuda"); wo = torch.zeros(nr + 1, dtype=torch.int64, device="cuda")
+        wk = torch.zeros(max(nw, 1) * READ_WALK.itemsize, dtype=torch.uint8, device="cuda")
+        sup = torch.zeros(max(nl, 1), dtype=torch.int64, device="cuda") if link_support else None
+        torch.cuda.synchronize()
+        if self.read_walks_device(*args, jn.data_ptr(), wo.data_ptr(), wk.data_ptr(), nw, sup.data_ptr() if link_support else None) != nw:
+            raise GkcError("the fill found another number of walks than the sizing call")
+        u64 = lambda t: t.cpu().numpy().view(np.uint64)
+        return dict(seg_offsets=u64(so), segments=seg.cpu().numpy()[: ns * READ_SEGMENT.itemsize].view(READ_SEGMENT).copy(), junction=u64(jn[:ns]), walk_offsets=u64(wo),
+                    walks=wk.cpu().numpy()[: nw * READ_WALK.itemsize].view(READ_WALK).copy(), link_offsets=u64(lo), links=u64(links),
+                    link_support=u64(sup[:nl]) if link_support else None)
+
     # ---- links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
     def unitig_links_device(self, d_masks=None):
         """the edges of the compacted graph as a CSR over the 2 n_unitigs sides -> (link_offsets int64[2 n_unitigs + 1], links int64[n_links]) as torch tensors on
@@ -895,9 +951,9 @@ class Counter:
             self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
         per_round = np.zeros(max(1, min(max_rounds, 64)), np.uint64)
         nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
-        self._tips = None; self._placement_nu = None
+        self._tips = None; self._placement_nu = None; self._placement_masks = None
         self._chk(self.L.gkc_graph_tips_remove(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), C.byref(nr), _p(per_round), C.byref(rem), C.byref(nu), C.byref(nb), C.byref(nc)))
-        self._placement_nu = nu.value
+        self._placement_nu = nu.value; self._placement_masks = masks
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, tips_per_round=[int(x) for x in per_round[: nr.value]], records_removed=rem.value,
                     n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value)
@@ -932,10 +988,10 @@ class Counter:
                 self._chk(self.L.gkc_graph_neighbors_solid(self.h, masks.data_ptr(), C.byref(n)))
         log = (SimplifyRound * SIMPLIFY_LOG_CAP)()
         nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
-        self._tips = None; self._placement_nu = None
+        self._tips = None; self._placement_nu = None; self._placement_masks = None
         self._chk(self.L.gkc_graph_simplify(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), log, SIMPLIFY_LOG_CAP, C.byref(nr), C.byref(rem), C.byref(nu), C.byref(nb),
                                             C.byref(nc)))
-        self._placement_nu = nu.value
+        self._placement_nu = nu.value; self._placement_masks = masks
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, records_removed=rem.value, n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value,
                     log=[(SIMPLIFY_KINDS[e.kind], int(e.sweep), int(e.n_unitigs), int(e.n_hits), int(e.n_records_removed)) for e in log[: min(nr.value, SIMPLIFY_LOG_CAP)]])
@@ -1003,6 +1059,47 @@ class Counter:
                         fields.append("L:%s:%d:%s" % (sign, int(e) >> 1, "-" if int(e) & 1 else "+"))
                 f.write(">" + " ".join(fields) + "\n" + text[b0:b1] + "\n")
         return len(kc), len(links)
+
+    def write_gfa(self, path, simplified=False, reads=None):
+        """the compacted graph as GFA 1 (gfa_text): the unitigs and links of unitigs() and unitig_links(), or, with ``simplified``, of simplified_unitigs(). reads =
+        (bases, offsets): a P line named r<read>_<walk> for every walk of read_walks that has at least two segments -> (n_unitigs, n_links, n_paths)"""
+        if simplified:
+            bases, offs, kc, lo, links = self.simplified_unitigs()
+        else:
+            keep, d_masks = self._masks_once(None)
+            bases, offs, kc = self.unitigs(d_masks)
+            lo, links = (t.cpu().numpy().view(np.uint64) for t in self._unitig_links_of_placement(len(kc), d_masks))
+        text = bases.tobytes().decode()
+        seqs = [text[int(offs[u]): int(offs[u + 1])] for u in range(len(kc))]
+        paths = None
+        if reads is not None:
+            w = self.read_walks(reads[0], reads[1], link_support=False)
+            paths = []
+            for r in range(len(w["walk_offsets"]) - 1):
+                for i, x in enumerate(w["walks"][int(w["walk_offsets"][r]): int(w["walk_offsets"][r + 1])]):
+                    if x["n_segments"] >= 2:
+                        s0 = int(x["first_segment"])
+                        paths.append(("r%d_%d" % (r, i), [int(v) for v in w["segments"]["node"][s0: s0 + int(x["n_segments"])]]))
+        with open(path, "w") as f:
+            f.write(gfa_text(self.k, seqs, kc, lo, links, paths))
+        return len(kc), len(links), 0 if paths is None else len(paths)
+
+
+def gfa_text(k, seqs, kc, link_offsets, links, walks=None):
+    """unitigs, links and read walks as GFA 1 -> str. Pure host code over arrays: seqs the unitig sequences (str or bytes), kc their abundance sums, link_offsets /
+    links the CSR of unitig_links() (slot 2 u + side holds entries v << 1 | mv). "H VN:Z:1.0"; per unitig "S <u> <sequence> KC:i:<kc[u]>"; per link entry
+    "L <u> <+|-> <v> <+|-> <k-1>M", the from-orientation + for side 0 (one leaves through the end of u) and - for side 1, the to-orientation + for mv = 0 (one arrives at
+    the begin of v) and - for mv = 1; walks: an iterable of (name, [node, ...]), node = unitig << 1 | strand, each "P <name> <u+|u-,...> *". Fields are tab-separated."""
+    lines = ["H\tVN:Z:1.0"]
+    for u, s in enumerate(seqs):
+        lines.append("S\t%d\t%s\tKC:i:%d" % (u, s if isinstance(s, str) else bytes(s).decode(), int(kc[u])))
+    lo = [int(x) for x in link_offsets]
+    for t in range(len(lo) - 1):
+        for e in links[lo[t]: lo[t + 1]]:
+            lines.append("L\t%d\t%s\t%d\t%s\t%dM" % (t >> 1, "+-"[t & 1], int(e) >> 1, "+-"[int(e) & 1], k - 1))
+    for name, nodes in (walks or ()):
+        lines.append("P\t%s\t%s\t*" % (name, ",".join("%d%s" % (int(n) >> 1, "+-"[int(n) & 1]) for n in nodes)))
+    return "\n".join(lines) + "\n"
 
 
 def balanced_owner_ranges(weights, world):

@@ -615,9 +615,32 @@ int gkc_graph_simplify(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const g
  *   support: d_support[u] = the sum of n_kmers over all segments on u, either strand.
  * State: the rules of the abundance queries, and for the nodes call (and for the segments call when d_support is given) a valid placement: GKC_ERR_ARG before a build
  * or after the results changed, as for gkc_graph_unitigs_write. Offsets are checked as gkc_query_reads_device checks them; bad offsets touch no memory outside the
- * buffers. Not served: the ranks of a communicator beyond the datasets a rank holds, and the merged state of a gkc_banks; whether consecutive segments of a read are
- * joined by an edge of the link CSR (paths across links); the correction of the reads.
- * Timing names of gkc_get_timing: "graph_read_nodes", "graph_read_segments" (the index: "query_index"). */
+ * buffers.
+ *   junction: of segment s, one u64: its relation to segment s + 1 of the SAME read. A = segment s, B = segment s + 1, gap = read_pos_B - (read_pos_A + n_kmers_A) (the
+ *            segments of a read are ascending and disjoint: gap >= 0); last_pos(A) = unitig_pos_A + (n_kmers_A - 1) on strand 0, unitig_pos_A - (n_kmers_A - 1) on
+ *            strand 1. The slot a segment leaves through is 2u + strand = node_A itself (strand 0 runs to the end of u, side 0; strand 1 to its begin, side 1), and the
+ *            entry that names how B is entered is node_B itself (strand 0 enters at the begin of v, mv = 0; strand 1 at its end, mv = 1): the lookup translates nothing.
+ *            The rules, in this order:
+ *            1. GKC_JUNCTION_END      : s is the last segment of its read.
+ *            2. a link entry index e  : gap == 0, A leaves at the extremity of its unitig (last_pos(A) == L_u - 1 on strand 0, == 0 on strand 1), B enters at one
+ *                                       (unitig_pos_B == 0 on strand 0, == L_v - 1 on strand 1), and slot node_A holds an entry equal to node_B: the index of that
+ *                                       entry in d_links, the lowest one if the slot holds the value twice (even k). Every value below GKC_JUNCTION_UNLINKED is a link index.
+ *            3. GKC_JUNCTION_UNLINKED : gap == 0 and rule 2 fails. With segments, links and placement of one graph this never occurs at odd k (two adjacent alive k-mers
+ *                                       of a read are neighbours, and neighbours that do not continue each other are extremities joined by a link); at even k a
+ *                                       palindromic record can produce it, and it is then the defined answer.
+ *            4. GKC_JUNCTION_COLLINEAR: gap > 0, node_B == node_A and unitig_pos_B == unitig_pos_A + (n_kmers_A + gap) on strand 0, - on strand 1: the read runs on along
+ *                                       the same unitig behind something of the same length (a substitution in the read, a same-length bulge that simplify removed). A
+ *                                       label; nothing is corrected.
+ *            5. GKC_JUNCTION_BREAK    : everything else with gap > 0.
+ *   walk   : a maximal run of consecutive segments of one read in which every junction is a link index: a path in the compacted graph that spells read bases
+ *            [read_pos_first, read_pos_first + n_kmers + k - 1). first_segment indexes d_segments; n_kmers is the sum over its segments (they are contiguous in the
+ *            read: read_pos_last + n_kmers_last - read_pos_first). The walks of a read are ascending, d_walk_offsets is the CSR over the reads, a read without
+ *            segments has no walk. n_walks = n_segments - (the junctions that are link indices).
+ *   link support: d_link_support[e] = the number of junctions whose value is e. Raw and per entry: at odd k the traversals in the other direction are counted on the
+ *            MIRROR entry (the mirror of e in slot 2u + su with value (v, mv) is the entry (u, 1 - su) in slot 2v + (1 - mv)); the two counts are not folded.
+ * Not served: the ranks of a communicator beyond the datasets a rank holds, and the merged state of a gkc_banks; walks across collinear gaps (a COLLINEAR junction ends
+ * a walk); the folded (mirror) support of a link; the correction of the reads; the drop-in.
+ * Timing names of gkc_get_timing: "graph_read_nodes", "graph_read_segments", "graph_read_walks" (the index: "query_index"). */
 #define GKC_NODE_REMOVED  (~0ull)        /* in the results, but a record of no unitig in this placement */
 #define GKC_NODE_ABSENT   (~0ull - 1)    /* a valid k-mer that is not in the results */
 #define GKC_NODE_NO_KMER  (~0ull - 2)    /* no k-mer starts here */
@@ -632,6 +655,21 @@ typedef struct gkc_read_segment { uint64_t node; uint32_t read_pos, unitig_pos, 
  * the array. No reads, or no bases: GKC_OK, every offset 0, *n_segments = 0. */
 int gkc_graph_reads_segments_device(gkc_ctx* ctx, const uint64_t* d_node, const uint32_t* d_pos, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
                                     uint64_t* d_seg_offsets, gkc_read_segment* d_segments, uint64_t cap_segments, uint64_t* n_segments, uint64_t* d_support);
+#define GKC_JUNCTION_END       (~0ull)        /* the last segment of its read */
+#define GKC_JUNCTION_BREAK     (~0ull - 1)    /* a gap, and not collinear */
+#define GKC_JUNCTION_COLLINEAR (~0ull - 2)    /* a gap, behind it the same unitig goes on where a piece of the gap's length would end */
+#define GKC_JUNCTION_UNLINKED  (~0ull - 3)    /* no gap, but no link entry joins the two segments; every value below this one is an index into d_links */
+typedef struct gkc_read_walk { uint64_t first_segment; uint32_t n_segments, n_kmers; } gkc_read_walk;   /* 16 bytes */
+/* d_seg_offsets (u64[n_reads + 1]), d_segments: what gkc_graph_reads_segments_device wrote; d_link_offsets (u64[2 n_unitigs + 1]), d_links (n_links entries): what
+ * gkc_graph_unitigs_links wrote for the placement the context holds; n_unitigs and the L_u are the placement's: GKC_ERR_ARG before a build or after the results changed.
+ * Fewer than 2^40 segments per call. d_walk_offsets: u64[n_reads + 1]; d_walks: room for cap_walks; both NULL: only *n_walks is reported and nothing is written; one
+ * without the other: GKC_ERR_ARG. Too small: GKC_ERR_CAPACITY, *n_walks reported, nothing written. d_junction (u64[n_segments]) and d_link_support (u64[n_links]), each
+ * or NULL, are written only by a call that writes walks; the support is zeroed, then filled. Found on the device, never by reading outside a buffer, and answered with
+ * GKC_ERR_ARG and no output written: d_seg_offsets is no CSR table over n_segments; two segments of a read overlap or descend; a node names a unitig >= n_unitigs; a
+ * slot's range is descending or not inside [0, n_links]. No reads, or no segments: GKC_OK, every offset 0, *n_walks = 0, the support zeroed when given. */
+int gkc_graph_reads_walks_device(gkc_ctx* ctx, const uint64_t* d_seg_offsets, const gkc_read_segment* d_segments, uint64_t n_reads, uint64_t n_segments,
+                                 const uint64_t* d_link_offsets, const uint64_t* d_links, uint64_t n_links, uint64_t* d_junction,
+                                 uint64_t* d_walk_offsets, gkc_read_walk* d_walks, uint64_t cap_walks, uint64_t* n_walks, uint64_t* d_link_support);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the

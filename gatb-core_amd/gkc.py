@@ -36,6 +36,7 @@ SYMBOLS = [
     "gkc_graph_unitigs_build", "gkc_graph_unitigs_write", "gkc_graph_unitigs_nodes", "gkc_graph_unitigs_links",
     "gkc_graph_unitigs_build_alive", "gkc_graph_tips_remove", "gkc_graph_simplify",
     "gkc_graph_reads_nodes_device", "gkc_graph_reads_segments_device", "gkc_graph_reads_walks_device",
+    "gkc_graph_reads_correct_device",
 ]
 
 # -solidity-kind of the reference (include/gkc.h GKC_SOLIDITY_*)
@@ -107,6 +108,16 @@ class ReadWalk(C.Structure):
 # gkc_read_walk as a numpy record, and the values of a junction that are no link index (GKC_JUNCTION_*)
 READ_WALK = np.dtype([("first_segment", np.uint64), ("n_segments", np.uint32), ("n_kmers", np.uint32)])
 JUNCTION_END, JUNCTION_BREAK, JUNCTION_COLLINEAR, JUNCTION_UNLINKED = (1 << 64) - 1, (1 << 64) - 2, (1 << 64) - 3, (1 << 64) - 4
+
+
+class CorrectParams(C.Structure):
+    """gkc_correct_params (include/gkc.h): 16 bytes"""
+    _fields_ = [("max_subst", C.c_uint32), ("ends", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+class CorrectStats(C.Structure):
+    """gkc_correct_stats (include/gkc.h): 56 bytes"""
+    _fields_ = [(n, C.c_uint64) for n in ("gaps_fixed", "gaps_skipped", "heads_fixed", "tails_fixed", "ends_skipped", "ends_no_room", "bases_changed")]
 
 
 # gkc_read_abundance (include/gkc.h) as a numpy record
@@ -248,6 +259,7 @@ def lib():
         "gkc_graph_reads_nodes_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp]),
         "gkc_graph_reads_segments_device": (C.c_int, [vp, vp, vp, vp, u64, u64, vp, vp, u64, P(u64), vp]),
         "gkc_graph_reads_walks_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, vp, u64, P(u64), vp]),
+        "gkc_graph_reads_correct_device": (C.c_int, [vp, vp, vp, u64, u64, vp, vp, u64, vp, vp, P(CorrectParams), vp, vp, vp, P(CorrectStats)]),
     }
     for name in SYMBOLS:
         f = getattr(L, name)          # raises AttributeError if the symbol is not exported
@@ -753,7 +765,7 @@ class Counter:
         nu, nb, nc = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._placement_nu = None; self._placement_masks = None      # (the plain build: its masks are those of the results, read_walks computes them when it needs them)
         self._chk(self.L.gkc_graph_unitigs_build(self.h, d_masks, C.byref(nu), C.byref(nb), C.byref(nc)))
-        self._placement_nu = nu.value
+        self._placement_nu = nu.value; self._placement_nb = nb.value
         return nu.value, nb.value, nc.value
 
     def unitigs_device(self, d_masks=None):
@@ -902,6 +914,49 @@ class Counter:
                     walks=wk.cpu().numpy()[: nw * READ_WALK.itemsize].view(READ_WALK).copy(), link_offsets=u64(lo), links=u64(links),
                     link_support=u64(sup[:nl]) if link_support else None)
 
+    def correct_reads_device(self, d_bases, d_offsets, n_reads, n_bases, d_seg_offsets, d_segments, n_segments, d_unitig_bases, d_unitig_offsets, d_out,
+                             max_subst=2, ends=True, d_n_changed=None, d_changed_bits=None, params=None):
+        """the reads rewritten to what the graph says (gkc_graph_reads_correct_device): device pointers, the segments read_segments_device wrote for these reads and the
+        unitig strings gkc_graph_unitigs_write wrote for the placement the context holds. d_out uint8[n_bases] (d_out == d_bases: in place), d_n_changed uint32[n_reads]
+        or None, d_changed_bits uint64[(n_bases + 63) // 64] or None; params: a CorrectParams, None with max_subst = ends = None for the library's default -> the stats
+        as a dict"""
+        if params is None and max_subst is not None:
+            params = CorrectParams(max_subst, 1 if ends else 0)
+        st = CorrectStats()
+        self._chk(self.L.gkc_graph_reads_correct_device(self.h, d_bases, d_offsets, n_reads, n_bases, d_seg_offsets, d_segments, n_segments, d_unitig_bases, d_unitig_offsets,
+                                                        None if params is None else C.byref(params), d_out, d_n_changed, d_changed_bits, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in CorrectStats._fields_}
+
+    def correct_reads(self, bases, offsets, max_subst=2, ends=True):
+        """the reads corrected against the placement this object built last (unitigs_build, remove_tips or simplify) -> dict: bases uint8[n_bases] (same offsets: only
+        substitutions), n_changed uint32[n_reads], changed bool[n_bases], stats (gaps_fixed, gaps_skipped, heads_fixed, tails_fixed, ends_skipped, ends_no_room,
+        bases_changed), seg_offsets and segments of the INPUT reads (as read_segments gives them). A stretch between two segments that continue each other along one
+        unitig, and a read's ends in front of its first / behind its last segment, become the unitig's bases when at most max_subst of them differ. The nodes call, the
+        segments calls, the unitig strings and the correction, all on the device."""
+        import torch
+        tb, to, nr, nb = self._reads_to_device(bases, offsets)
+        node = torch.zeros(max(nb, 2), dtype=torch.int64, device="cuda"); pos = torch.zeros(max(nb, 4), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        self.read_nodes_device(tb.data_ptr(), to.data_ptr(), nr, nb, node.data_ptr(), pos.data_ptr())
+        nu = getattr(self, "_placement_nu", None)
+        if nu is None:
+            raise GkcError("the placement in the context was not built through this object (unitigs_build, remove_tips or simplify first)")
+        nub = self._placement_nb
+        ns = self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb)
+        so = torch.zeros(nr + 1, dtype=torch.int64, device="cuda"); seg = torch.zeros(max(ns, 1) * READ_SEGMENT.itemsize, dtype=torch.uint8, device="cuda")
+        ub = torch.zeros(max(nub, 16), dtype=torch.uint8, device="cuda"); uo = torch.zeros(nu + 1, dtype=torch.int64, device="cuda")
+        out = torch.zeros(max(nb, 16), dtype=torch.uint8, device="cuda"); nch = torch.zeros(max(nr, 1), dtype=torch.int32, device="cuda")
+        bits = torch.zeros((nb + 63) // 64 + 1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        if self.read_segments_device(node.data_ptr(), pos.data_ptr(), to.data_ptr(), nr, nb, so.data_ptr(), seg.data_ptr(), ns) != ns:
+            raise GkcError("the fill found another number of segments than the sizing call")
+        self._chk(self.L.gkc_graph_unitigs_write(self.h, ub.data_ptr(), nub, uo.data_ptr(), nu, None))
+        stats = self.correct_reads_device(tb.data_ptr(), to.data_ptr(), nr, nb, so.data_ptr(), seg.data_ptr(), ns, ub.data_ptr(), uo.data_ptr(), out.data_ptr(), max_subst, ends,
+                                          nch.data_ptr(), bits.data_ptr())
+        changed = np.unpackbits(bits.cpu().numpy().view(np.uint8), bitorder="little")[:nb].astype(bool)
+        return dict(bases=out[:nb].cpu().numpy(), n_changed=nch[:nr].cpu().numpy().view(np.uint32), changed=changed, stats=stats,
+                    seg_offsets=so.cpu().numpy().view(np.uint64), segments=seg.cpu().numpy()[: ns * READ_SEGMENT.itemsize].view(READ_SEGMENT).copy())
+
     # ---- links between the unitigs (include/gkc.h, "unitigs": side, slot, entry)
     def unitig_links_device(self, d_masks=None):
         """the edges of the compacted graph as a CSR over the 2 n_unitigs sides -> (link_offsets int64[2 n_unitigs + 1], links int64[n_links]) as torch tensors on
@@ -953,7 +1008,7 @@ class Counter:
         nr, rem, nu, nb, nc = (C.c_uint64() for _ in range(5))
         self._tips = None; self._placement_nu = None; self._placement_masks = None
         self._chk(self.L.gkc_graph_tips_remove(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), C.byref(nr), _p(per_round), C.byref(rem), C.byref(nu), C.byref(nb), C.byref(nc)))
-        self._placement_nu = nu.value; self._placement_masks = masks
+        self._placement_nu = nu.value; self._placement_nb = nb.value; self._placement_masks = masks
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, tips_per_round=[int(x) for x in per_round[: nr.value]], records_removed=rem.value,
                     n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value)
@@ -991,7 +1046,7 @@ class Counter:
         self._tips = None; self._placement_nu = None; self._placement_masks = None
         self._chk(self.L.gkc_graph_simplify(self.h, masks.data_ptr(), alive.data_ptr(), C.byref(prm), log, SIMPLIFY_LOG_CAP, C.byref(nr), C.byref(rem), C.byref(nu), C.byref(nb),
                                             C.byref(nc)))
-        self._placement_nu = nu.value; self._placement_masks = masks
+        self._placement_nu = nu.value; self._placement_nb = nb.value; self._placement_masks = masks
         self._tips = dict(masks=masks, alive=alive, n=n.value, n_unitigs=nu.value, n_bases=nb.value)
         return dict(alive=alive[: n.value].cpu().numpy().astype(bool), rounds=nr.value, records_removed=rem.value, n_unitigs=nu.value, n_bases=nb.value, n_cycles=nc.value,
                     log=[(SIMPLIFY_KINDS[e.kind], int(e.sweep), int(e.n_unitigs), int(e.n_hits), int(e.n_records_removed)) for e in log[: min(nr.value, SIMPLIFY_LOG_CAP)]])
@@ -1083,6 +1138,20 @@ class Counter:
         with open(path, "w") as f:
             f.write(gfa_text(self.k, seqs, kc, lo, links, paths))
         return len(kc), len(links), 0 if paths is None else len(paths)
+
+
+def write_corrected_fasta(path, bases, offsets, names=None):
+    """the reads of a flat buffer (correct_reads(...)["bases"] with the offsets of the input) as FASTA, one record per read: ">" + names[r] (None: the read's number) and
+    the sequence on one line. Host code -> the number of reads"""
+    raw = np.ascontiguousarray(bases, dtype=np.uint8).tobytes()
+    offs = [int(x) for x in offsets]
+    if names is not None and len(names) != len(offs) - 1:
+        raise GkcError("%d names for %d reads" % (len(names), len(offs) - 1))
+    with open(path, "wb") as f:
+        for r in range(len(offs) - 1):
+            name = ("%d" % r) if names is None else names[r]
+            f.write(b">" + (name if isinstance(name, bytes) else str(name).encode()) + b"\n" + raw[offs[r]: offs[r + 1]] + b"\n")
+    return len(offs) - 1
 
 
 def gfa_text(k, seqs, kc, link_offsets, links, walks=None):

@@ -638,9 +638,23 @@ int gkc_graph_simplify(gkc_ctx* ctx, uint8_t* d_masks, uint8_t* d_alive, const g
  *            segments has no walk. n_walks = n_segments - (the junctions that are link indices).
  *   link support: d_link_support[e] = the number of junctions whose value is e. Raw and per entry: at odd k the traversals in the other direction are counted on the
  *            MIRROR entry (the mirror of e in slot 2u + su with value (v, mv) is the entry (u, 1 - su) in slot 2v + (1 - mv)); the two counts are not folded.
+ *   map    : a segment on node 2u + strand with its first k-mer at (read_pos, unitig_pos) gives read position x of its read a unitig base: on strand 0 base
+ *            unitig_pos + (x - read_pos) of unitig u as gkc_graph_unitigs_write emits it, on strand 1 the COMPLEMENT of base unitig_pos + k - 1 - (x - read_pos).
+ *   region : a stretch of a read that no k-mer of a segment covers and that one segment's map reaches. Three kinds, each handled on its own:
+ *            gap : A, B consecutive in one read and in the COLLINEAR relation of rule 4; read positions [read_pos_A + n_kmers_A + k - 1, read_pos_B), targets from A's
+ *                  map (collinearity keeps them inside the unitig). Empty when gap < k (a cycle's cut can give that): nothing is done and nothing counted.
+ *            head: (params.ends) the first segment F of the read has read_pos_F > 0: [0, read_pos_F), targets from F's map. ROOM is required: strand 0
+ *                  unitig_pos_F >= read_pos_F, strand 1 unitig_pos_F + read_pos_F <= L_u - 1. Without room the region is left alone and counted as ends_no_room.
+ *            tail: (params.ends) the last segment Z leaves t = len - (read_pos_Z + n_kmers_Z + k - 1) > 0 bases: the last t bases, targets from Z's map. Room: strand 0
+ *                  unitig_pos_Z + n_kmers_Z - 1 + t <= L_u - 1, strand 1 unitig_pos_Z - (n_kmers_Z - 1) >= t.
+ *   correction: the CHANGES of a region are the positions whose input byte differs from the target byte (targets are upper-case ACGT: an N or a lower-case letter is a
+ *            change). changes <= params.max_subst: the region's bytes become the targets (gaps_fixed / heads_fixed / tails_fixed); otherwise it is left alone
+ *            (gaps_skipped / ends_skipped). Whole or not at all. Every other byte of the output equals the input: substitutions only, lengths and offsets never change, a
+ *            read without a segment is copied. The regions of a read are disjoint: the result does not depend on the order they are evaluated in.
  * Not served: the ranks of a communicator beyond the datasets a rank holds, and the merged state of a gkc_banks; walks across collinear gaps (a COLLINEAR junction ends
- * a walk); the folded (mirror) support of a link; the correction of the reads; the drop-in.
- * Timing names of gkc_get_timing: "graph_read_nodes", "graph_read_segments", "graph_read_walks" (the index: "query_index"). */
+ * a walk), also across corrected ones; the folded (mirror) support of a link; of the correction: gaps whose two sides lie on different unitigs (an error next to a
+ * branching node), insertions and deletions, a choice between alternatives by coverage; the drop-in.
+ * Timing names of gkc_get_timing: "graph_read_nodes", "graph_read_segments", "graph_read_walks", "graph_read_correct" (the index: "query_index"). */
 #define GKC_NODE_REMOVED  (~0ull)        /* in the results, but a record of no unitig in this placement */
 #define GKC_NODE_ABSENT   (~0ull - 1)    /* a valid k-mer that is not in the results */
 #define GKC_NODE_NO_KMER  (~0ull - 2)    /* no k-mer starts here */
@@ -670,6 +684,22 @@ typedef struct gkc_read_walk { uint64_t first_segment; uint32_t n_segments, n_km
 int gkc_graph_reads_walks_device(gkc_ctx* ctx, const uint64_t* d_seg_offsets, const gkc_read_segment* d_segments, uint64_t n_reads, uint64_t n_segments,
                                  const uint64_t* d_link_offsets, const uint64_t* d_links, uint64_t n_links, uint64_t* d_junction,
                                  uint64_t* d_walk_offsets, gkc_read_walk* d_walks, uint64_t cap_walks, uint64_t* n_walks, uint64_t* d_link_support);
+typedef struct gkc_correct_params { uint32_t max_subst; uint32_t ends; uint32_t pad[2]; } gkc_correct_params;   /* NULL: {2, 1} */
+typedef struct gkc_correct_stats  { uint64_t gaps_fixed, gaps_skipped, heads_fixed, tails_fixed, ends_skipped, ends_no_room, bases_changed; } gkc_correct_stats;
+/* The reads rewritten to what the graph says ("region", "correction" above). d_bases, d_offsets, n_reads, n_bases: the reads, as for gkc_graph_reads_nodes_device (16-byte
+ * aligned, fewer than 2^40 bases, no read of 2^32 bases or more); d_seg_offsets, d_segments, n_segments (fewer than 2^40): what gkc_graph_reads_segments_device wrote for
+ * them; d_unitig_bases, d_unitig_offsets: what gkc_graph_unitigs_write wrote for the placement the context holds; n_unitigs and the L_u are the placement's: GKC_ERR_ARG
+ * before a build or after the results changed. d_out: char[n_bases], 16-byte aligned; it may EQUAL d_bases (in place, nothing is copied), any other overlap is GKC_ERR_ARG.
+ * d_n_changed (u32[n_reads]: the bases changed per read) and d_changed_bits (u64[(n_bases + 63) / 64]: bit g & 63 of word g >> 6 is set where byte g changed), each or
+ * NULL, are fully written by a successful call. stats: host, or NULL. Found on the device before anything is written, never by reading outside a buffer, and answered
+ * with GKC_ERR_ARG and no output touched: d_offsets or d_seg_offsets is no CSR table; two segments of a read overlap or descend; a segment runs past its read (read_pos +
+ * n_kmers + k - 1 > len); a node names a unitig >= n_unitigs; a segment holds no k-mer or its unitig range leaves [0, L_u); d_unitig_offsets[0] != 0 or
+ * d_unitig_offsets[u + 1] - d_unitig_offsets[u] != L_u + k - 1 for some u (the strings of another placement). No reads, or no segments: GKC_OK, the output is a copy, the
+ * stats are zero. */
+int gkc_graph_reads_correct_device(gkc_ctx* ctx, const char* d_bases, const uint64_t* d_offsets, uint64_t n_reads, uint64_t n_bases,
+                                   const uint64_t* d_seg_offsets, const gkc_read_segment* d_segments, uint64_t n_segments,
+                                   const char* d_unitig_bases, const uint64_t* d_unitig_offsets,
+                                   const gkc_correct_params* params, char* d_out, uint32_t* d_n_changed, uint64_t* d_changed_bits, gkc_correct_stats* stats);
 
 /* ---- input: FASTA / FASTQ text -> flat bases + offsets ON THE DEVICE ------------------------------------
  * Replaces BankFasta::Iterator::get_next_seq_from_file (bank/impl/BankFasta.cpp:488-571, buffered_gets :425-483) and the
